@@ -12,8 +12,12 @@ synthetic 1x30x600 grey lines x~U[0,1), 20 labels/line, English alphabet (V=96),
 dropout 0.5, fp32.  One step = train() of src/train_cnn_lstm.py:131-150: forward + CTC + backward + (RCCL all-reduce of
 the flat gradient) + clamp(+-5) + Adam, returning the loss as a Python float.  SURVEY.md §8(d) counts the H2D copy of the image
 batch as part of the step, so `value` is the loop fed from a pinned HOST batch (2.3 MB over PCIe inside train()); the same K steps
-with the batch already resident in HBM are the side number `resident_input` (the two agree within box noise).
-Prints ONE JSON line on rank 0; exits non-zero if the parity leg finds a label mismatch or a CTC-loss error above 1e-3."""
+with the batch already resident in HBM are the side number `resident_input` of --full (the two agree within box noise).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (metric, value, unit, dtype, ms_per_step, ...).
+`--full` adds the side measurements and checks: the resident-input loop, the per-family kernel events and the roofline, the
+per-entry-point breakdown, the host enqueue time, the GEMM launches alone, the all-reduce times and, on one rank, the parity leg and
+the CPU baseline; it exits non-zero if the parity leg finds a label mismatch or a CTC-loss error above 1e-3.
+`--dump-outputs DIR` writes what the last timed step left to its caller as DIR/<name>.npy (see dump_outputs)."""
 import argparse
 import json
 import os
@@ -118,6 +122,29 @@ def parity_inputs(hidden, vocab):
     seed = PARITY_BATCH_SEED if PARITY_BATCH_SEED is not None else WL["parity_seed"]
     x, w, tgt, tl = cf.closed_form_batch(B, 1, WL["himg"], WL["widths"], vocab, WL["labels"], seed=seed)
     return sd_np, x, w, tgt, tl
+
+
+DUMP_BUDGET_ELEMS = 14 << 20      # 56 MiB of float32 over all arrays of --dump-outputs
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of train() holds after the last timed step: the loss it returned (loss.npy, float64) and the model's state that
+    the step updated in place, parameters and BatchNorm buffers, as <state-dict key>.npy (float32; integer buffers float64).  Arrays
+    are written whole, smallest first, while each fits its share of DUMP_BUDGET_ELEMS; a larger one is written as a 1-D sample at flat
+    indices drawn without replacement by numpy RandomState(0) and sorted, so the same arguments give the same sample on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    state = [(k, v.detach().cpu().numpy()) for k, v in model.state_dict().items()]
+    left, todo = DUMP_BUDGET_ELEMS, len(state)
+    for name, a in sorted(state, key=lambda kv: kv[1].size):
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        share = left // todo
+        if a.size > share:
+            a = a.ravel()[np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.size * a.itemsize // 4
+        todo -= 1
 
 
 def conv_flops(args):
@@ -487,10 +514,10 @@ def run_rank(args):
     x_host, tgt, widths, tl = make_batch(rank, len(al))
     x_host = x_host.pin_memory()
 
-    # ---- parity leg, GPU side (rank 0, N=1): one forward of the closed-form parity batch with closed-form weights, fixed pool
+    # ---- parity leg (--full), GPU side (rank 0, N=1): one forward of the closed-form parity batch with closed-form weights, fixed pool
     # samples and dropout off; the CPU oracle (child process) repeats it and compares loss / greedy labels
     parity_file = None
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if want_cpu:
         init_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
         sd_np, xp, wp, tgtp, tlp = parity_inputs(args.hidden, len(al))
@@ -560,49 +587,76 @@ def run_rank(args):
     import gc
     gc.collect()
     gc.freeze()
-    # Two timed loops of exactly K steps each, both bracketed by barrier + synchronize; the side number (batch resident in HBM) first.
-    dt_res, _ = timed(batch_dev, args.steps)
-    # timed region (headline): the batch comes from pinned host memory inside train().  HIP events, on the stream each kernel is
-    # launched on, around every launch of the MFMA kernel families in every `event_every`-th step only (an event pair costs the queue
-    # a few microseconds of overlap: ~70 pairs slow that step by a few percent); the full per-entry-point breakdown comes from a
-    # separate un-timed pass below
-    _lib.enable_timing(MFMA_NAMES)
-    dt, final_loss = timed(batch_host, args.steps, event_every=args.event_every)
-    timed_recs = {k: list(v) for k, v in _lib.timing_records().items()}
-    comm_ms = opt.comm_times_ms()
-    sampled_steps = max(1, len(range(0, args.steps, args.event_every)) if args.event_every else 0)
-    _lib.enable_timing(None)
-    opt.time_comm(False)
-    names = MFMA_NAMES + ["vocr_bn_train_stats", "vocr_bn_relu_apply", "vocr_bn_relu_fracpool2x2_fwd", "vocr_bn_train_relu_apply",
-                          "vocr_bn_train_relu_fracpool2x2_fwd", "vocr_bn_relu_bwd",
-                          "vocr_fracpool2x2_bwd", "vocr_bn_relu_fracpool2x2_bwd", "vocr_ctc_loss_grad", "vocr_clamp_adam", "vocr_bchw_to_wbch", "vocr_wbch_to_bchw",
-                          "vocr_relu_maxpool2_fwd", "vocr_relu_maxpool2_bwd", "vocr_gather_rows", "vocr_dropout_fwd", "vocr_mul", "vocr_f32_to_f16_layouts", "vocr_conv3x3_c1_fwd", "vocr_conv3x3_c1_wgrad",
-                          "vocr_gemm_x6_split", "vocr_gemm_h3_split"]
-    _lib.enable_timing(names)
-    for _ in range(PROFILE_STEPS):
-        va.train(batch_dev, model, crit, opt)
-    torch.cuda.synchronize()
-    prof = _lib.timing_records()
-    _lib.enable_timing(None)
-    # host side of a step: how long the Python + ctypes layer takes to ENQUEUE one step (train_async(): no readback of the loss), measured
-    # on an idle queue over 4 steps - far fewer launches than the queue holds, so nothing here waits for the device.  If this number
-    # approaches ms_per_step the step is launch-bound and faster kernels buy nothing.
-    torch.cuda.synchronize()
-    enq = []
-    for _ in range(4):
-        t_e = time.perf_counter()
-        va.train_async(batch_dev, model, crit, opt)
-        enq.append(1000.0 * (time.perf_counter() - t_e))
-    torch.cuda.synchronize()
-    opt.check_health()
+    # Timed loops of exactly K steps each, bracketed by barrier + synchronize.  --full times a side number first: the same K steps with
+    # the batch resident in HBM.
+    if args.full:
+        dt_res, _ = timed(batch_dev, args.steps)
+        # HIP events, on the stream each kernel is launched on, around every launch of the MFMA kernel families in every `event_every`-th
+        # step of the headline loop only (an event pair costs the queue a few microseconds of overlap: ~70 pairs slow that step by a few
+        # percent); the full per-entry-point breakdown comes from a separate un-timed pass below
+        _lib.enable_timing(MFMA_NAMES)
+    # timed region (headline): the batch comes from pinned host memory inside train()
+    dt, final_loss = timed(batch_host, args.steps, event_every=args.event_every if args.full else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, final_loss)
     ranks_seen = dist.get_world_size() if use_dist else 1
-    alone = gemm_alone(args.hidden) if rank == 0 and args.hidden == 512 and args.config == "c1" and not args.no_gemm_alone else None
+    if args.full:
+        timed_recs = {k: list(v) for k, v in _lib.timing_records().items()}
+        comm_ms = opt.comm_times_ms()
+        sampled_steps = max(1, len(range(0, args.steps, args.event_every)) if args.event_every else 0)
+        _lib.enable_timing(None)
+        opt.time_comm(False)
+        names = MFMA_NAMES + ["vocr_bn_train_stats", "vocr_bn_relu_apply", "vocr_bn_relu_fracpool2x2_fwd", "vocr_bn_train_relu_apply",
+                              "vocr_bn_train_relu_fracpool2x2_fwd", "vocr_bn_relu_bwd",
+                              "vocr_fracpool2x2_bwd", "vocr_bn_relu_fracpool2x2_bwd", "vocr_ctc_loss_grad", "vocr_clamp_adam", "vocr_bchw_to_wbch", "vocr_wbch_to_bchw",
+                              "vocr_relu_maxpool2_fwd", "vocr_relu_maxpool2_bwd", "vocr_gather_rows", "vocr_dropout_fwd", "vocr_mul", "vocr_f32_to_f16_layouts", "vocr_conv3x3_c1_fwd", "vocr_conv3x3_c1_wgrad",
+                              "vocr_gemm_x6_split", "vocr_gemm_h3_split"]
+        _lib.enable_timing(names)
+        for _ in range(PROFILE_STEPS):
+            va.train(batch_dev, model, crit, opt)
+        torch.cuda.synchronize()
+        prof = _lib.timing_records()
+        _lib.enable_timing(None)
+        # host side of a step: how long the Python + ctypes layer takes to ENQUEUE one step (train_async(): no readback of the loss), measured
+        # on an idle queue over 4 steps - far fewer launches than the queue holds, so nothing here waits for the device.  If this number
+        # approaches ms_per_step the step is launch-bound and faster kernels buy nothing.
+        torch.cuda.synchronize()
+        enq = []
+        for _ in range(4):
+            t_e = time.perf_counter()
+            va.train_async(batch_dev, model, crit, opt)
+            enq.append(1000.0 * (time.perf_counter() - t_e))
+        torch.cuda.synchronize()
+        opt.check_health()
+        alone = gemm_alone(args.hidden) if rank == 0 and args.hidden == 512 and args.config == "c1" and not args.no_gemm_alone else None
 
     out = None
     parity_failed = None
     if rank == 0:
         ms = 1000.0 * dt / args.steps
         value = B * world * args.steps / dt
+        out = {
+            "metric": "line-images/sec (train, batch 32, 30x600 grey)" if args.config == "c1" else
+                      "line-images/sec (train, batch 32) - SIDE line for BASELINE %s, not the headline metric" % {"c4": "configs[3]", "c5": "configs[4]"}[args.config],
+            "value": round(value, 2), "unit": "line-images/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": ("f32" if conv_dtype == "fp32" else "f32 with fp16 conv operands (fp32 accumulate)") +
+                     {"bf16x6": " (the LSTM's large GEMMs as bf16x6 products: fp32 operands split exactly into three bf16 planes, six bf16 MFMAs per fp32 "
+                                "product, fp32 accumulate; VOCR_LSTM_GEMM=f32 restores the f32-MFMA kernels)",
+                      "fp16x3": " - OPT-IN MODE, NOT THE HEADLINE CONFIGURATION: the LSTM's large GEMMs as fp16x3 products (VOCR_LSTM_GEMM=fp16x3: operands "
+                                "approximated by two fp16 planes with per-row scales, three fp16 MFMAs per product, fp32 accumulate)",
+                      "f32": ""}[lstm_gemm_mode()], "data": "synthetic",
+            "config": {"workload": wl["what"] + ", 3xBiLSTM-%d, train() = H2D of the batch + fwd+CTC+bwd+allreduce+clamp+Adam, loss returned as a float" % args.hidden,
+                       "name": args.config, "widths": "%d .. %d px, mean %.0f" % (min(wl["widths"]), max(wl["widths"]), sum(wl["widths"]) / float(B)),
+                       "conv_dtype": conv_dtype,
+                       "global_batch": B * world, "parallelism": "dp%d" % world, "ranks_seen": ranks_seen,
+                       "backend": (args.backend + ("/RCCL" if args.backend == "nccl" else "")) if use_dist else "none",
+                       "final_loss": round(float(final_loss), 3), "per_rank_rng": "seed 1234 + 1000*rank after an identical init"},
+            "ms_per_step_ranks": {"min": round(1000.0 * rank_dt[0] / args.steps, 3), "max": round(1000.0 * rank_dt[1] / args.steps, 3),
+                                  "what": "slowest and fastest rank's wall time per step over the timed loop (ms_per_step is the max): a gap = a straggler"},
+        }
+    if rank == 0 and args.full:
         peak = F32_MFMA_PEAK_TFLOPS
 
         def fam_stats(recs, per_step_div):
@@ -667,28 +721,9 @@ def run_rank(args):
         for name, lst in prof.items():
             if lst:
                 breakdown[name] = round(sum(e0.elapsed_time(e1) for _, e0, e1 in lst) / PROFILE_STEPS, 3)
-        out = {
-            "metric": "line-images/sec (train, batch 32, 30x600 grey)" if args.config == "c1" else
-                      "line-images/sec (train, batch 32) - SIDE line for BASELINE %s, not the headline metric" % {"c4": "configs[3]", "c5": "configs[4]"}[args.config],
-            "value": round(value, 2), "unit": "line-images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("f32" if conv_dtype == "fp32" else "f32 with fp16 conv operands (fp32 accumulate)") +
-                     {"bf16x6": " (the LSTM's large GEMMs as bf16x6 products: fp32 operands split exactly into three bf16 planes, six bf16 MFMAs per fp32 "
-                                "product, fp32 accumulate; VOCR_LSTM_GEMM=f32 restores the f32-MFMA kernels)",
-                      "fp16x3": " - OPT-IN MODE, NOT THE HEADLINE CONFIGURATION: the LSTM's large GEMMs as fp16x3 products (VOCR_LSTM_GEMM=fp16x3: operands "
-                                "approximated by two fp16 planes with per-row scales, three fp16 MFMAs per product, fp32 accumulate)",
-                      "f32": ""}[lstm_gemm_mode()], "data": "synthetic",
-            "config": {"workload": wl["what"] + ", 3xBiLSTM-%d, train() = H2D of the batch + fwd+CTC+bwd+allreduce+clamp+Adam, loss returned as a float" % args.hidden,
-                       "name": args.config, "widths": "%d .. %d px, mean %.0f" % (min(wl["widths"]), max(wl["widths"]), sum(wl["widths"]) / float(B)),
-                       "conv_dtype": conv_dtype,
-                       "global_batch": B * world, "parallelism": "dp%d" % world, "ranks_seen": ranks_seen,
-                       "backend": (args.backend + ("/RCCL" if args.backend == "nccl" else "")) if use_dist else "none",
-                       "final_loss": round(float(final_loss), 3), "per_rank_rng": "seed 1234 + 1000*rank after an identical init"},
+        out.update({
             "resident_input": {"value": round(B * world * args.steps / dt_res, 2), "ms_per_step": round(1000.0 * dt_res / args.steps, 3),
                                "what": "same K steps with the image batch already in HBM (no H2D inside train()); runs before the headline loop"},
-            "ms_per_step_ranks": {"min": round(1000.0 * rank_dt[0] / args.steps, 3), "max": round(1000.0 * rank_dt[1] / args.steps, 3),
-                                  "what": "slowest and fastest rank's wall time per step over the timed loop (ms_per_step is the max): a gap = a straggler"},
             "allreduce_ms_per_step": comm_ms,
             "host_enqueue_ms_per_step": {"mean": round(sum(enq) / len(enq), 3), "min": round(min(enq), 3), "share_of_step": round(sum(enq) / len(enq) / ms, 3),
                                          "what": "wall time of train_async() (enqueue only, no loss readback) on an idle queue, 4 steps, no profiler"},
@@ -710,7 +745,7 @@ def run_rank(args):
                                                 "the f32 matrix peak" + ("" if conv_dtype == "fp32" else " - the fp16-operand conv launches of this configuration run on "
                                                 "the 16x faster fp16 pipe, so this fraction mixes two rooflines: read families_in_step")}},
             "ms_per_step_by_entry_point": breakdown,
-        }
+        })
         if want_cpu:
             out.update(cpu_leg(parity_file, args.config))
             par = out.get("parity")
@@ -757,9 +792,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gemm-alone", action="store_true", help="skip the alone-on-the-chip GEMM launches (profiling passes that average per launch)")
-    ap.add_argument("--event-every", type=int, default=10, help="HIP events around the dominant kernel in every n-th timed step (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks: resident-input loop, kernel events and roofline, per-entry-point breakdown, "
+                         "host enqueue time, GEMM launches alone, all-reduce times, parity leg against the CPU oracle and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the model state the last timed step left as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the parity leg and the CPU baseline")
+    ap.add_argument("--no-gemm-alone", action="store_true", help="with --full: skip the alone-on-the-chip GEMM launches (profiling passes that average per launch)")
+    ap.add_argument("--event-every", type=int, default=10, help="with --full: HIP events around the dominant kernel in every n-th timed step (0: none)")
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--config", default="c1", choices=sorted(WORKLOADS),
                     help="c1 = BASELINE configs[1], the headline metric; c4 / c5 = configs[3] / configs[4] as side lines of the same JSON shape")

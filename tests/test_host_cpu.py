@@ -230,6 +230,37 @@ def test_bench_flop_accounting_of_the_minimal_filtering_kernels():
     assert sorted(b.WORKLOADS) == ["c1", "c4", "c5"]
 
 
+def test_bench_dump_outputs_are_whole_or_a_fixed_sample_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: the loss and every state-dict entry of the headline model (3 x BiLSTM-512) as float32 / float64 .npy,
+    the same bytes on a second call, under 64 MB in all; the entries that do not fit their share are fixed samples of their elements."""
+    import importlib.util
+    import vistaocr_amd as va
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    torch.manual_seed(0)
+    m = va.CnnOcrModel(alphabet=va.english_alphabet(), verbose=False, gpu=False, **b.HP)
+    sd = m.state_dict()
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), m, 1234.5)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["loss.npy"] + [k + ".npy" for k in sd]) == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) < 64e6
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1234.5]
+    sampled = 0
+    for k, v in sd.items():
+        a, a2 = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, a2)
+        full = v.numpy().astype(a.dtype)
+        if a.shape == full.shape:
+            assert np.array_equal(a, full), k
+        else:
+            sampled += 1
+            assert a.ndim == 1 and a.size < full.size and np.isin(a, full.ravel()).all(), k
+    assert 0 < sampled < 8
+
+
 def test_packed_row_count_is_the_layouts_formula():
     """include/vocr.h: rows = 4 * (sum of the chains' longest lengths + chains + 1); a uniform batch of B % 4 == 0 lines packs to more rows
     than T*B (the zero groups), which is why CnnOcrModel keeps such a batch dense (pack_threshold)."""

@@ -453,7 +453,7 @@ def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it: the parent spawns two rank processes (here on ONE GPU, gloo
     backend, per-step LSTM launches: a plumbing test of the launcher, the env contract, the two-bucket exchange inside the
     backward and the single JSON line)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
                         "--share-gpu", "--hidden", "256"], capture_output=True, text=True, timeout=900,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2000:])
@@ -462,3 +462,19 @@ def test_bench_launches_its_own_ranks():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["ranks_seen"] == 2 and out["config"]["global_batch"] == 64 and out["scaling"] == "weak"
     assert out["value"] > 0 and "roofline" in out and "cpu_baseline" not in out
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """`python bench.py` without --full: one timed loop of --steps steps and the headline fields, none of the side legs; --dump-outputs
+    writes the loss of the last timed step (the one the line's final_loss rounds) and the model state beside it."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600,
+                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2000:])
+    out = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+    assert all(k in out for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert not {"resident_input", "roofline", "parity", "cpu_baseline", "allreduce_ms_per_step", "ms_per_step_by_entry_point"} & set(out)
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float64 and round(float(loss[0]), 3) == out["config"]["final_loss"]
+    assert np.isfinite(np.load(tmp_path / "prob_layer.0.weight.npy")).all()

@@ -224,11 +224,14 @@ def test_gemm_pair_modes(m, n, k):
 
 def test_a_process_group_does_not_cost_the_step_its_overlap():
     """Regression guard for the hardware-queue trap: with a process group initialised (RCCL, one rank) the step must take
-    what it takes without one.  An extra stream created on the data-parallel path once cost 3.4 of 18.5 ms; the bound is generous."""
+    what it takes without one.  An extra stream created on the data-parallel path once cost 3.4 of 18.5 ms; the bound is generous.
+    Both runs get the package's 8 hardware queues explicitly: the package only sets a default, so a GPU_MAX_HW_QUEUES inherited from
+    the caller's environment would win and bring back the trap this test guards against."""
     def run(extra_env):
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+        env["GPU_MAX_HW_QUEUES"] = "8"
         env.update(extra_env)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
                            capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr[-1500:]
         return json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
