@@ -420,6 +420,24 @@ int vocr_argmax_rows(const float* x, int32_t* idx, float* maxv, int rows, int v,
 int vocr_greedy_collapse(const int32_t* idx, const float* maxv, const int32_t* lens, const int32_t* canon,
                          int32_t* out_labels, int32_t* out_counts, int t, int b, float thresh, void* stream);
 
+/* ---- CTC prefix beam search with a character n-gram LM: the search of decode_with_lm — decoder.py:11-109, cnnlstm.py:298-475 ---- */
+/* The eesen WFST of the reference is replaced by a character n-gram given as backoff-resolved dense tables over lm_states states:
+ * lm_logp[S][V] = ln P(c | state) (backoff applied), lm_next[S][V] = the state after c, lm_eos[S] = ln P(</s> | state), lm_start
+ * the <s> state; all three NULL: no LM.  logits[T][B][V] raw (log-softmax inside), lens[B] device int32 (clamped to [0, T]).
+ * canon[V] as for vocr_greedy_collapse (NULL: identity): columns of one class are one symbol (logsumexp of the members) and the
+ * emitted labels are canonical indices.  Candidates are ranked by logsumexp(p_blank, p_nonblank) + lm_weight * LM +
+ * insertion_bonus * length (total order: score, then parent rank and class, so results are bit-identical from run to run);
+ * prune_logp: classes whose frame log-prob is below it are not extended (-INFINITY: off).  1 <= beam <= 128,
+ * 1 <= nbest <= beam, v <= 256.  Outputs, best first: out_labels[B][nbest][T] (zero past the length), out_lens[B][nbest],
+ * out_scores[B][nbest][3] = {total, acoustic (CTC log-prob of the labelling), LM log-prob including </s>}; a rank the search
+ * did not fill has length 0 and total -inf.  Workspace (the prefix node pool, T*beam nodes per line) from
+ * vocr_ctc_beam_workspace_bytes (0 for an unsupported shape). */
+size_t vocr_ctc_beam_workspace_bytes(int t, int b, int v, int beam, int nbest);
+int vocr_ctc_beam_search(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam, int nbest,
+                         const float* lm_logp, const int32_t* lm_next, const float* lm_eos, int lm_states, int lm_start,
+                         float lm_weight, float insertion_bonus, float prune_logp, int32_t* out_labels, int32_t* out_lens,
+                         float* out_scores, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

@@ -105,6 +105,8 @@ SIGNATURES = {
     "vocr_ctc_loss_grad": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "vocr_argmax_rows": (I, [P, P, P, I, I, P]),
     "vocr_greedy_collapse": (I, [P, P, P, P, P, P, I, I, F, P]),
+    "vocr_ctc_beam_workspace_bytes": (Z, [I, I, I, I, I]),
+    "vocr_ctc_beam_search": (I, [P, P, I, I, I, P, I, I, P, P, P, I, I, F, F, F, P, P, P, P, Z, P]),
     "vocr_clamp_adam": (I, [P, P, P, P, Z, F, F, F, F, F, F, F, I, P, P]),
     "vocr_clamp": (I, [P, Z, F, P, P]),
     "vocr_comm_unique_id": (I, [P]),

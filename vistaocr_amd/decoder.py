@@ -71,3 +71,62 @@ class ArgmaxDecoder:
     def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
         alphabet = self.alphabet if lang is None else self.alphabet[lang]
         return decode_greedy(model_output, batch_actual_timesteps, alphabet, uxxxx=uxxxx)
+
+
+class BeamDecoder:
+    """CTC prefix beam search on the GPU (vocr_ctc_beam_search), optionally with a character n-gram LM (vistaocr_amd.lm.CharNgramLM):
+    the stand-in for the reference's LM decode (decode_with_lm, src/decoder.py:11-109).  Hypotheses are ranked by
+    ln P_ctc(y | x) + lm_weight * ln P_lm(y </s>) + insertion_bonus * |y|; `prune_logp` (None: off) skips extensions by symbols whose
+    frame log-probability is below it.  Symbols with the same alphabet string are one symbol, as in the greedy decode."""
+
+    def __init__(self, alphabet, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None):
+        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
+            raise ValueError("BeamDecoder: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (beam, nbest))
+        if lm is not None and lm.logp.shape[1] != len(alphabet):
+            raise ValueError("BeamDecoder: the LM was resolved for %d symbols, the alphabet has %d" % (lm.logp.shape[1], len(alphabet)))
+        self.alphabet = alphabet
+        self.beam, self.nbest = int(beam), int(nbest)
+        self.lm, self.lm_weight, self.insertion_bonus, self.prune_logp = lm, float(lm_weight), float(insertion_bonus), prune_logp
+        self._canon = {}
+
+    def _search(self, model_output, batch_actual_timesteps, nbest):
+        dev = model_output.device
+        key = str(dev)
+        if key not in self._canon:
+            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        lens = batch_actual_timesteps
+        if torch.is_tensor(lens):
+            lens = lens.detach().cpu()
+        labels, lengths, scores = ops.ctc_beam_search(model_output.detach(), [int(v) for v in lens], self._canon[key], self.beam, nbest,
+                                                      self.lm.to(dev) if self.lm is not None else None, self.lm_weight,
+                                                      self.insertion_bonus, self.prune_logp)
+        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
+
+    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
+        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; labels are canonical alphabet indices,
+        acoustic the CTC log-probability of the labelling, lm the LM log-probability including </s> (0 without an LM)."""
+        nbest = self.nbest if nbest is None else int(nbest)
+        labels, lengths, scores = self._search(model_output, batch_actual_timesteps, nbest)
+        out = []
+        for b in range(labels.shape[0]):
+            hyps = []
+            for q in range(nbest):
+                if not np.isfinite(scores[b, q, 0]):
+                    break
+                hyps.append(([int(v) for v in labels[b, q, :lengths[b, q]]], tuple(float(s) for s in scores[b, q])))
+            out.append(hyps)
+        return out
+
+    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
+        """The best hypothesis of each line in decode_greedy's format: space-joined uxxxx tokens, converted to utf8 unless uxxxx."""
+        if lang is not None:
+            raise ValueError("BeamDecoder: one alphabet per decoder (lang is not supported)")
+        labels, lengths, scores = self._search(model_output, batch_actual_timesteps, 1)
+        idx_to_char = self.alphabet.idx_to_char
+        result = []
+        for b in range(labels.shape[0]):
+            n = int(lengths[b, 0]) if np.isfinite(scores[b, 0, 0]) else 0
+            result.append(" ".join(idx_to_char[int(k)] for k in labels[b, 0, :n]))
+        if uxxxx == False:  # noqa: E712  (decode_greedy's comparison)
+            result = [uxxxx_to_utf8(r) for r in result]
+        return result

@@ -246,13 +246,15 @@ def _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataload
     return hist
 
 
-def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7):
+def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None):
     """The inference driver of src/decode_testset.py:42-206 without the LM branch: forward every batch, greedy-decode,
     and write `hyp-chars.txt` ("<uxxxx ...> (<utt-id>)") and `hyp-chars.txt.utf8` ("<utf8> (<utt-id minus last _part>)").
     The reference runs the decode in a background process because its per-frame numpy argmax is slow; here the argmax
     is a GPU kernel and one small D2H copy, so decode runs inline.  `visual_to_logical` stands in for the ICU bidi step
     (`utf8_visual_to_logical`, src/textutils.py:186-212; identity for left-to-right scripts).  Seeds like the reference
-    (FractionalMaxPool draws samples in eval too, decode_testset.py:70-71).  Returns the number of lines written."""
+    (FractionalMaxPool draws samples in eval too, decode_testset.py:70-71).  `decoder`: an object with the ArgmaxDecoder /
+    BeamDecoder `.decode(model_output, lens, uxxxx=False)` interface that produces the hypotheses instead of the greedy decode
+    (None: the greedy decode); the files have the same format either way.  Returns the number of lines written."""
     import os
     from .textutils import utf8_to_uxxxx
     torch.manual_seed(seed)
@@ -265,7 +267,7 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7):
             open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8:
         for x, _target, widths, _target_lens, meta in dataloader:
             out, lens = model(x.cuda(non_blocking=True), widths)
-            hyps = model.decode_without_lm(out, lens, uxxxx=False)
+            hyps = model.decode_without_lm(out, lens, uxxxx=False) if decoder is None else decoder.decode(out, lens, uxxxx=False)
             for i, hyp in enumerate(hyps):
                 hyp_utf8 = visual_to_logical(hyp) if visual_to_logical is not None else hyp
                 uttid = meta["utt-ids"][i]

@@ -1245,3 +1245,47 @@ def clamp_(x, clamp):
         raise RuntimeError("vistaocr_amd.clamp_: need a contiguous fp32 tensor")
     call("vocr_clamp", _p(x), x.numel(), float(clamp), _p(health(x.device)), _stream())
     return x
+
+
+def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None):
+    """CTC prefix beam search (vocr_ctc_beam_search) over raw logits [T,B,V].  `lens`: the frames of each line (any int sequence or
+    tensor), `canon`: int32 [V] device tensor of the symbol classes or None, `lm`: a dict of the device tables lm_logp [S,V] fp32,
+    lm_next [S,V] int32, lm_eos [S] fp32 and the int `start` (CharNgramLM.to(device)) or None.
+    Returns (labels int32 [B,nbest,T], lengths int32 [B,nbest], scores fp32 [B,nbest,3] = total, acoustic, LM), on the device."""
+    _need_gpu(logits)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    dev = logits.device
+    lib = _lib.load()
+    nbytes = lib.vocr_ctc_beam_workspace_bytes(T, B, V, int(beam), int(nbest))
+    if nbytes == 0:
+        raise RuntimeError("ctc_beam_search: unsupported shape or beam (T=%d B=%d V=%d beam=%d nbest=%d; V <= 256, 1 <= nbest <= beam "
+                           "<= 128)" % (T, B, V, beam, nbest))
+    if torch.is_tensor(lens):
+        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    if lens_dev.numel() != B:
+        raise RuntimeError("ctc_beam_search: %d lengths for %d lines" % (lens_dev.numel(), B))
+    if canon is not None:
+        _need_gpu(canon)
+        if canon.dtype != torch.int32 or canon.numel() != V:
+            raise RuntimeError("ctc_beam_search: canon must be int32 [V]")
+    labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    if lm is not None:
+        lp, nx, eos = lm["lm_logp"], lm["lm_next"], lm["lm_eos"]
+        _need_gpu(lp, nx, eos)
+        S = lp.shape[0]
+        if lp.shape != (S, V) or nx.shape != (S, V) or eos.shape != (S,) or lp.dtype != torch.float32 or nx.dtype != torch.int32:
+            raise RuntimeError("ctc_beam_search: LM tables do not match V=%d (lm_logp %s, lm_next %s, lm_eos %s)"
+                               % (V, tuple(lp.shape), tuple(nx.shape), tuple(eos.shape)))
+        lm_args = (_p(lp), _p(nx), _p(eos), S, int(lm["start"]))
+    else:
+        lm_args = (None, None, None, 0, 0)
+    prune = float("-inf") if prune_logp is None else float(prune_logp)
+    call("vocr_ctc_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), *lm_args, float(lm_weight),
+         float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores), _p(ws), ws.numel() * 4, _stream())
+    return labels, out_lens, scores
