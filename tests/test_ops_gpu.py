@@ -433,9 +433,9 @@ def test_permute_and_elementwise(dev):
     assert torch.allclose(o[kept], a[kept] * 2)
 
 
-def _ref_bilstm(x, lens, params, H):
+def _ref_bilstm(x, lens, params, H, dtype=torch.float32):
     T, B, D = x.shape
-    m = torch.nn.LSTM(D, H, num_layers=1, bidirectional=True)
+    m = torch.nn.LSTM(D, H, num_layers=1, bidirectional=True).to(dtype)
     with torch.no_grad():
         for name, p in zip(["weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse",
                             "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse"], params):

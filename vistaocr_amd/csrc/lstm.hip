@@ -1124,9 +1124,14 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
         return;
     }
     // the cell thread's own element of step t: plane-local row = sr.base + sr.stride*t + crow.  Addresses = a wave-uniform 64-bit base of
-    // the step (scalar arithmetic) + a 32-bit per-thread byte offset that never changes (the planes stay below 2 GB: host check)
+    // the direction and the step (scalar arithmetic) + a 32-bit per-thread byte offset that never changes.  The direction's plane is in
+    // the base, so an offset stays inside ONE direction's plane: < rows * 4H * 4 bytes (gates, xproj) = 2 x the 2-GB y plane the host
+    // checks (rows * 2H * 4 < 2^31), which an unsigned offset holds (with dir * rows in the offset, the reverse direction's gates and
+    // xproj offsets passed 2^32 from rows * H >= 2^27 on and wrapped silently into the forward plane)
     const long crow0 = (long)dir * sr.total + sr.base + crow;
-    const unsigned cvoff = (unsigned)((crow0 * H + unit) * 4);                          // cell; gates: x 4
+    const unsigned cvoff = (unsigned)((((long)sr.base + crow) * H + unit) * 4);        // cell; gates: x 4
+    float* const gates_d = gates + (long)dir * sr.total * 4 * H;
+    float* const cell_d = cell + (long)dir * sr.total * H;
     const unsigned yvoff = (unsigned)((((long)sr.base + crow) * 2 * H + dir * H + unit) * 4);
     const unsigned rvoff = (unsigned)(((member * 4 + crow) * 32 + cu) * 4);             // hand-off ring block of this member
     float cstate = 0.f;
@@ -1144,13 +1149,15 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
         const int kk = kbase + 4 * (lane >> 2);
         poff = (((kk >> 5) * 4 + prow) * 32 + (kk & 31)) * 4;
     }
-    const unsigned xvoff = (unsigned)((((long)dir * sr.total + sr.base + (erowok ? erow : 0)) * 4 * H + (long)egate * H + unit0 + eu) * 4);
+    const unsigned xvoff = (unsigned)((((long)sr.base + (erowok ? erow : 0)) * 4 * H + (long)egate * H + unit0 + eu) * 4);
     const long xstep = (long)sr.stride * 4 * H * 4;                // bytes per time step
+    const char* const xproj_d = (const char*)(xproj + (long)dir * sr.total * 4 * H);                   // this direction's plane
+    const char* const xproj2_d = xproj2 ? (const char*)(xproj2 + (long)dir * sr.total * 4 * H) : nullptr;
     auto x_load = [&](int st) {
         const int tt = dir == 0 ? st : Tc - 1 - st;
-        float v = *(const float*)((const char*)xproj + tt * xstep + xvoff);
+        float v = *(const float*)(xproj_d + tt * xstep + xvoff);
         // second addend: the other source direction's plane of the layer below (xproj_follow_waves writes one plane per direction)
-        if (xproj2) v += *(const float*)((const char*)xproj2 + tt * xstep + xvoff);
+        if (xproj2_d) v += *(const float*)(xproj2_d + tt * xstep + xvoff);
         return v;
     };
     float xn = s0 < s1 ? x_load(s0) : 0.f;
@@ -1249,8 +1256,8 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
                 if (step >= 2) sstore_b32_sc1(xr, rvoff, kHandoffSentinel);
             }
             sstore_b32((const char*)y + srow * (2 * H * 4), yvoff, h);
-            sstore_b128((const char*)gates + srow * (H * 16), cvoff << 2, gv);
-            sstore_b32((const char*)cell + srow * (H * 4), cvoff, c);
+            sstore_b128((const char*)gates_d + srow * (H * 16), cvoff << 2, gv);
+            sstore_b32((const char*)cell_d + srow * (H * 4), cvoff, c);
         }
         if (tid < 128 && lane == 0) __hip_atomic_store(&sig[wave], step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         LSTM_STAMP(5);              // cell update + stores issued (waves 0, 1)
@@ -2168,7 +2175,8 @@ static int lstm_fwd_impl(const float* xproj, const float* whh_fwd, const float* 
                       aligned16(gates);
     VOCR_CHECK_ARG(aligned16(gates), "vocr_lstm_fwd: gates must be 16-byte aligned");
     const dim3 grid(2 * (h / 4));
-    // the chain kernels address y through a buffer descriptor with 32-bit byte offsets
+    // the chain kernels address y through a buffer descriptor with 32-bit byte offsets, and the wide 4-row sweep forms unsigned per-thread
+    // byte offsets into one direction's plane of gates / xproj (< rows * 4H * 4 = 2 x the y bound below: lstm_fwd_chain4w)
     const bool fits32 = (packed_rows ? (long)packed_rows : (long)t * b) * 2 * h * 4 < (1l << 31);
     const SweepKind kind = lstm_sweep_kind(false, b, h, fast && fits32 && 8 * (h / 16) <= resident_workgroup_capacity());
     if (packed_rows) {

@@ -720,7 +720,7 @@ def lstm_gemm():
 
 def x6_layer_ok(T, B, H, rows):
     """The BiLSTM layer's large GEMMs run as split products (any row layout; the recurrent weight gradient joins them when its time shift -
-    B rows dense, 4 packed - is a whole number of k16 steps)."""
+    B rows dense, 4 packed - is a whole number of k16 steps and 4H is a multiple of 256)."""
     return lstm_gemm() != "f32" and (4 * H) % 128 == 0 and (rows if rows else T * B) >= 256
 
 
@@ -1131,10 +1131,12 @@ class BiLstmLayerFn(torch.autograd.Function):
                 dgt = x6_planes(dg[0], 2 * G, R, False, G, x2=dg[1], seg=G, axis=1)
                 xt = x6_planes(x, din, R, False, din, bound=ctx.x_bound)
                 gemm_x6(dgt, 2 * G, R, xt, din, R, 2 * G, din, k16, dwi_f, din, c1=dwi_r, rsplit=G)
-                if T > 1 and sh % 16 == 0 and (R - sh) % 16 == 0:
-                    # the recurrent product's time shift (sh rows = sh / 16 k16 steps) is a k window of the same planes and of the output's transpose
+                if T > 1 and sh % 16 == 0 and (R - sh) % 16 == 0 and G % 256 == 0:
+                    # the recurrent product's time shift (sh rows = sh / 16 k16 steps) is a k window of the same planes and of the output's transpose;
+                    # the reverse direction's rows start at row G of the 2G-row plane set, which a view can only do on a 256-row tile boundary
+                    # (G = 128 (2j + 1), H % 64 == 32, takes gemm_pair below)
                     yt = x6_planes(y, 2 * H, R, False, 2 * H, bound=1.0)       # |h| = |o tanh(c)| <= 1
-                    if G % 256 == 0 and _X6_TWO_VIEWS:
+                    if _X6_TWO_VIEWS:
                         # both directions in one launch: forward rows = dg_f[sh:]^T . y[:-sh, :H], reverse rows = dg_r[:-sh]^T . y[sh:, H:]
                         gemm_x6_two_views(dgt, 2 * G, R, yt, 2 * H, R, 2 * G, H, R - sh, G, (sh // 16, 0, 0), (0, H, sh // 16), dwh_f, dwh_r, H)
                     else:
