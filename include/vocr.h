@@ -438,6 +438,27 @@ int vocr_ctc_beam_search(const float* logits, const int32_t* lens, int t, int b,
                          float lm_weight, float insertion_bonus, float prune_logp, int32_t* out_labels, int32_t* out_lens,
                          float* out_scores, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC prefix beam search with a word n-gram and a lexicon: the TLG.fst decode of decode_with_lm — decoder.py:11-109 ---- */
+/* The search, inputs, limits and outputs of vocr_ctc_beam_search (no pruning); hypotheses are scored by a word n-gram over the tokens
+ * of form_tokenized_words (textutils.py:290-323).  cls_kind[V]: 1 letter, 2 space (u0020), 3 single (punctuation / digit, a token of
+ * its own, cls_tok[V] its LM token), 0 none.  Letter runs are words, limited to the lexicon trie trie_next[trie_nodes][V] (-1: no
+ * child, root 0), trie_tok[trie_nodes] (the word ending at a node, -1: none), trie_la[trie_nodes] (the largest 1-gram ln P below the
+ * node: the look-ahead of an open word).  LM over lm_tokens token ids: lm_states states (0 = the empty history, every history's
+ * back-off state lm_back[s] < s), successors of state s at lm_off[s]..lm_off[s+1] of lm_succ_tok (sorted) / lm_succ_logp (ln) /
+ * lm_succ_next (state 0: dense over all tokens, lm_off[1] = lm_tokens), lm_bow[S] the ln backoff weights; lm_succ entries in all.
+ * A candidate is ranked by logsumexp(p_blank, p_nonblank) + lm_weight * (LM of the closed tokens + look-ahead of the open word) +
+ * word_bonus * closed tokens; a word outside the lexicon scores ln P(<unk>) + oov_penalty (-INFINITY: closed vocabulary, such words
+ * are never hypotheses).  The final score closes the open word and adds ln P(</s>) (tok_eos); out_scores = {total, acoustic, LM}.
+ * Workspace from vocr_ctc_word_beam_workspace_bytes (0 for an unsupported shape). */
+size_t vocr_ctc_word_beam_workspace_bytes(int t, int b, int v, int beam, int nbest);
+int vocr_ctc_word_beam_search(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam, int nbest,
+                              const int32_t* cls_kind, const int32_t* cls_tok, const int32_t* trie_next, const int32_t* trie_tok,
+                              const float* trie_la, int trie_nodes, const int32_t* lm_off, const int32_t* lm_succ_tok,
+                              const float* lm_succ_logp, const int32_t* lm_succ_next, const float* lm_bow, const int32_t* lm_back,
+                              int lm_states, int lm_succ, int lm_tokens, int lm_start, int tok_unk, int tok_eos, float lm_weight,
+                              float word_bonus, float oov_penalty, int32_t* out_labels, int32_t* out_lens, float* out_scores,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

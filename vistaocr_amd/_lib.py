@@ -107,6 +107,9 @@ SIGNATURES = {
     "vocr_greedy_collapse": (I, [P, P, P, P, P, P, I, I, F, P]),
     "vocr_ctc_beam_workspace_bytes": (Z, [I, I, I, I, I]),
     "vocr_ctc_beam_search": (I, [P, P, I, I, I, P, I, I, P, P, P, I, I, F, F, F, P, P, P, P, Z, P]),
+    "vocr_ctc_word_beam_workspace_bytes": (Z, [I, I, I, I, I]),
+    "vocr_ctc_word_beam_search": (I, [P, P, I, I, I, P, I, I, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, I, F, F, F, P, P, P, P,
+                                      Z, P]),
     "vocr_clamp_adam": (I, [P, P, P, P, Z, F, F, F, F, F, F, F, I, P, P]),
     "vocr_clamp": (I, [P, Z, F, P, P]),
     "vocr_comm_unique_id": (I, [P]),

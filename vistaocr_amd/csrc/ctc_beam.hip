@@ -29,64 +29,14 @@
 // LM: backoff-resolved dense tables over S states, lm_logp[S][V] (natural log), lm_next[S][V], lm_eos[S]; a candidate costs one
 // load of each, coalesced over c.  State indices read from lm_next outside [0, S) fall back to lm_start (never an out-of-range load).
 // prune_logp: classes whose frame log-prob is below it are not extended (-inf: off, the exact search).
-#include "vocr_common.h"
+//
+// Steps 1, 2 (the merge lookup), 4 and the backtrack are the device functions of ctc_beam_common.h, shared with the word search
+// (ctc_word_beam.hip); this file holds the character LM's candidate scoring and beam state.
+#include "ctc_beam_common.h"
 
 namespace {
 
-constexpr int BT = 256;            // threads per line
-constexpr int KMAX = 128;
-constexpr int VMAX = 256;
-constexpr float NEG_INF = -INFINITY;
-
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == NEG_INF) return NEG_INF;
-    return m + logf(expf(a - m) + expf(b - m));
-}
-
-// order-preserving map of a non-NaN float to uint32 (larger score -> larger key)
-__device__ __forceinline__ unsigned score_key(float s) {
-    const unsigned u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ unsigned long long hash_push(unsigned long long h, int c) {
-    return (h ^ (unsigned long long)(c + 1)) * 0x100000001b3ull + 0x9e3779b97f4a7c15ull;
-}
-
-// inclusive prefix sum over the 256 threads (every thread calls it)
-__device__ __forceinline__ int block_scan(int v, int* wsum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int n = __shfl_up(v, o, 64);
-        if (lane >= o) v += n;
-    }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    int add = 0;
-    for (int i = 0; i < w; ++i) add += wsum[i];
-    __syncthreads();
-    return v + add;
-}
-
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
+using namespace ctcbeam;
 
 struct BeamBuf {
     float pb[KMAX], pnb[KMAX], acc[KMAX];
@@ -102,15 +52,10 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
                                                       float* __restrict__ out_scores, int2* __restrict__ pool_all) {
     extern __shared__ float s_score[];                 // [K*V]
     __shared__ BeamBuf s_beam[2];
-    __shared__ float s_lp[VMAX], s_xp[VMAX], s_row[VMAX];
-    __shared__ int s_cls[VMAX], s_chain[VMAX];
-    __shared__ float s_spb[KMAX], s_spnb[KMAX];
-    __shared__ int s_merge[KMAX], s_selid[KMAX], s_order[KMAX];
-    __shared__ unsigned s_selkey[KMAX];
-    __shared__ int s_hist[256];
-    __shared__ int s_wsum[4];
-    __shared__ float s_red[4];
-    __shared__ int s_bin, s_before, s_eqcnt, s_total, s_nsel;
+    __shared__ Frame s_f;
+    __shared__ Select s_sel;
+    __shared__ float s_spb[KMAX], s_spnb[KMAX], s_fin[KMAX];
+    __shared__ int s_merge[KMAX];
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -119,23 +64,11 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
     const int len_b = min(max(lens[b], 0), T);
     int2* pool = pool_all + (long)b * T * K;
 
-    // symbol classes: sanitised canon (an entry that is not a canonical index <= v stands for itself), member chains
-    if (tid < V) {
-        int c = canon ? canon[tid] : tid;
-        if (c < 0 || c > tid || (canon && canon[c] != c)) c = tid;
-        s_cls[tid] = c;
-    }
-    __syncthreads();
-    if (tid < V) {
-        int nx = -1;
-        for (int w = tid + 1; w < V; ++w)
-            if (s_cls[w] == s_cls[tid]) { nx = w; break; }
-        s_chain[tid] = nx;
-    }
+    init_classes(canon, V, s_f);
     if (tid == 0) {
         BeamBuf& B0 = s_beam[0];
         B0.pb[0] = 0.f; B0.pnb[0] = NEG_INF; B0.acc[0] = 0.f; B0.last[0] = -1; B0.len[0] = 0; B0.lms[0] = start;
-        B0.node[0] = -1; B0.hash[0] = 0x84222325cbf29ce4ull; B0.phash[0] = 0;
+        B0.node[0] = -1; B0.hash[0] = HASH_ROOT; B0.phash[0] = 0;
     }
     int cur = 0, nb = 1;
     __syncthreads();
@@ -144,58 +77,21 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
         const BeamBuf& C = s_beam[cur];
         BeamBuf& N = s_beam[cur ^ 1];
         // 1. log-softmax of the row, class log-probs
-        const float x = tid < V ? logits[((long)t * B + b) * V + tid] : NEG_INF;
-        const float m = block_max(x, s_red);
-        const float se = block_sum(tid < V && m != NEG_INF ? expf(x - m) : 0.f, s_red);
-        const float lse = m + logf(se);
-        if (tid < V) s_row[tid] = x - lse;
-        __syncthreads();
-        if (tid < V) {
-            float lp = NEG_INF;
-            if (s_cls[tid] == tid) {
-                float mm = NEG_INF;
-                for (int v = tid; v >= 0; v = s_chain[v]) mm = fmaxf(mm, s_row[v]);
-                if (s_chain[tid] < 0) {
-                    lp = s_row[tid];
-                } else if (mm != NEG_INF) {
-                    float ss = 0.f;
-                    for (int v = tid; v >= 0; v = s_chain[v]) ss += expf(s_row[v] - mm);
-                    lp = mm + logf(ss);
-                }
-            }
-            s_lp[tid] = lp;
-            s_xp[tid] = (tid > 0 && lp > NEG_INF && lp >= prune) ? lp : NEG_INF;
-        }
-        __syncthreads();
+        frame_logprobs(logits + ((long)t * B + b) * V, V, prune, s_f);
 
         // 2. stay probabilities and the merge of the extension that re-creates beam j from its parent prefix
         if (tid < nb) {
             const int j = tid;
             const int lj = C.len[j], cj = C.last[j];
-            int mk = -1;
-            if (lj > 0 && s_xp[cj] > NEG_INF) {
-                const int pj = (C.node[j] >= 0 && C.node[j] < T * K) ? pool[C.node[j]].x : -1;
-                for (int k = 0; k < nb && mk < 0; ++k) {
-                    if (C.len[k] != lj - 1 || C.hash[k] != C.phash[j]) continue;
-                    int a = C.node[k], p = pj;
-                    bool same = true;
-                    while (a != p) {                  // equal lengths: both chains reach the root (-1) together
-                        if (a < 0 || p < 0 || a >= T * K || p >= T * K) { same = false; break; }
-                        const int2 na = pool[a], np = pool[p];
-                        if (na.y != np.y) { same = false; break; }
-                        a = na.x; p = np.x;
-                    }
-                    if (same) mk = k;
-                }
-            }
+            const int mk = find_merge(j, nb, C.len, C.last, C.node, C.hash, C.phash, s_f.xp, pool, T * K);
             s_merge[j] = mk;
             const float pbj = C.pb[j], pnbj = C.pnb[j];
-            float spnb = lj > 0 ? pnbj + s_lp[cj] : NEG_INF;
+            float spnb = lj > 0 ? pnbj + s_f.lp[cj] : NEG_INF;
             if (mk >= 0) {
                 const float base = (cj == C.last[mk]) ? C.pb[mk] : lse2(C.pb[mk], C.pnb[mk]);
-                spnb = lse2(spnb, base + s_xp[cj]);
+                spnb = lse2(spnb, base + s_f.xp[cj]);
             }
-            s_spb[j] = lse2(pbj, pnbj) + s_lp[0];
+            s_spb[j] = lse2(pbj, pnbj) + s_f.lp[0];
             s_spnb[j] = spnb;
         }
         __syncthreads();
@@ -209,7 +105,7 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
                 const float ac = lse2(s_spb[k], s_spnb[k]);
                 sc = ac + (has_lm && alpha != 0.f ? alpha * C.acc[k] : 0.f) + beta * (float)C.len[k];
             } else {
-                const float xp = s_xp[c];
+                const float xp = s_f.xp[c];
                 if (xp == NEG_INF) {
                     sc = NEG_INF;
                 } else {
@@ -222,83 +118,14 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
         }
         __syncthreads();
         if (tid < nb && s_merge[tid] >= 0) s_score[s_merge[tid] * V + C.last[tid]] = NEG_INF;
-        if (tid == 0) s_nsel = 0;
         __syncthreads();
 
         // 4. top K under (score desc, id asc)
-        unsigned prefix = 0, mask = 0;
-        int need = K;
-        bool take_all = false;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < ncand; i += BT) {
-                const float sc = s_score[i];
-                if (!(sc > NEG_INF)) continue;
-                const unsigned u = score_key(sc);
-                if ((u & mask) == prefix) atomicAdd(&s_hist[(u >> shift) & 255], 1);
-            }
-            __syncthreads();
-            const int cnt = s_hist[255 - tid];
-            const int incl = block_scan(cnt, s_wsum);
-            if (shift == 24 && tid == BT - 1) s_total = incl;
-            if (incl >= need && incl - cnt < need) { s_bin = 255 - tid; s_before = incl - cnt; s_eqcnt = cnt; }
-            __syncthreads();
-            if (shift == 24 && s_total <= K) { take_all = true; break; }
-            need -= s_before;
-            prefix |= (unsigned)s_bin << shift;
-            mask |= 255u << shift;
-            __syncthreads();                              // s_bin / s_before are rewritten by the next pass
-        }
-        int id_cut = 0x7fffffff;
-        if (!take_all && s_eqcnt > need) {                // ties at the K-th score: the smallest ids among them
-            int idp = 0, idm = 0;
-            for (int shift = 8; shift >= 0; shift -= 8) {
-                s_hist[tid] = 0;
-                __syncthreads();
-                for (int i = tid; i < ncand; i += BT) {
-                    const float sc = s_score[i];
-                    if (!(sc > NEG_INF) || score_key(sc) != prefix || (i & idm) != idp) continue;
-                    atomicAdd(&s_hist[(i >> shift) & 255], 1);
-                }
-                __syncthreads();
-                const int cnt = s_hist[tid];
-                const int incl = block_scan(cnt, s_wsum);
-                if (incl >= need && incl - cnt < need) { s_bin = tid; s_before = incl - cnt; }
-                __syncthreads();
-                need -= s_before;
-                idp |= s_bin << shift;
-                idm |= 255 << shift;
-                __syncthreads();
-            }
-            id_cut = idp;
-        }
-        for (int i = tid; i < ncand; i += BT) {
-            const float sc = s_score[i];
-            if (!(sc > NEG_INF)) continue;
-            const unsigned u = score_key(sc);
-            if (take_all || u > prefix || (u == prefix && i <= id_cut)) {
-                const int slot = atomicAdd(&s_nsel, 1);
-                if (slot < KMAX) { s_selid[slot] = i; s_selkey[slot] = u; }
-            }
-        }
-        __syncthreads();
-        const int nsel = min(s_nsel, K);
-        if (tid < nsel) {
-            const unsigned u = s_selkey[tid];
-            const int id = s_selid[tid];
-            int r = 0;
-            for (int q = 0; q < nsel; ++q) {
-                const unsigned uq = s_selkey[q];
-                r += (uq > u || (uq == u && s_selid[q] < id)) ? 1 : 0;
-            }
-            s_order[r] = id;
-        }
-        __syncthreads();
+        const int nsel = top_k(s_score, ncand, K, s_sel);
 
         // 5. the new beams, in rank order
         if (tid < nsel) {
-            const int q = tid, id = s_order[q];
+            const int q = tid, id = s_sel.order[q];
             const int k = id / V, c = id - k * V;
             if (c == 0) {
                 N.pb[q] = s_spb[k]; N.pnb[q] = s_spnb[k]; N.acc[q] = C.acc[k]; N.last[q] = C.last[k]; N.len[q] = C.len[k];
@@ -306,7 +133,7 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
             } else {
                 const int node = t * K + q;
                 N.pb[q] = NEG_INF;
-                N.pnb[q] = ((c == C.last[k]) ? C.pb[k] : lse2(C.pb[k], C.pnb[k])) + s_xp[c];
+                N.pnb[q] = ((c == C.last[k]) ? C.pb[k] : lse2(C.pb[k], C.pnb[k])) + s_f.xp[c];
                 if (has_lm) {
                     const long e = (long)C.lms[k] * V + c;
                     const int ns = lm_next[e];
@@ -332,41 +159,15 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
         const float lmt = has_lm ? C.acc[tid] + lm_eos[C.lms[tid]] : 0.f;
         s_spb[tid] = lse2(C.pb[tid], C.pnb[tid]);
         s_spnb[tid] = lmt;
-        s_lp[tid] = s_spb[tid] + (has_lm && alpha != 0.f ? alpha * lmt : 0.f) + beta * (float)C.len[tid];
+        s_fin[tid] = s_spb[tid] + (has_lm && alpha != 0.f ? alpha * lmt : 0.f) + beta * (float)C.len[tid];
     }
     __syncthreads();
-    if (tid < nb) {
-        const float f = s_lp[tid];
-        const unsigned u = f == f ? score_key(f) : 0u;     // NaN ranks last
-        int r = 0;
-        for (int q = 0; q < nb; ++q) {
-            const float fq = s_lp[q];
-            const unsigned uq = fq == fq ? score_key(fq) : 0u;
-            r += (uq > u || (uq == u && q < tid)) ? 1 : 0;
-        }
-        s_order[r] = tid;
-    }
-    __syncthreads();
+    rank_final(s_fin, nb, s_sel.order);
     if (tid < nbest) {
         const int q = tid;
-        int32_t* lab = out_labels + ((long)b * nbest + q) * T;
-        float* sc = out_scores + ((long)b * nbest + q) * 3;
-        int n = 0;
-        if (q < nb) {
-            const int j = s_order[q];
-            n = min(C.len[j], T);
-            int node = C.node[j];
-            for (int p = n - 1; p >= 0; --p) {
-                int2 nd = (node >= 0 && node < T * K) ? pool[node] : make_int2(-1, 0);
-                lab[p] = nd.y;
-                node = nd.x;
-            }
-            sc[0] = s_lp[j]; sc[1] = s_spb[j]; sc[2] = s_spnb[j];
-        } else {
-            sc[0] = NEG_INF; sc[1] = NEG_INF; sc[2] = 0.f;
-        }
-        for (int p = n; p < T; ++p) lab[p] = 0;
-        out_lens[(long)b * nbest + q] = n;
+        const int j = q < nb ? s_sel.order[q] : 0;
+        write_hyp(b, q, nbest, T, q < nb, C.len[j], C.node[j], s_fin[j], s_spb[j], s_spnb[j], pool, T * K, out_labels, out_lens,
+                  out_scores);
     }
 }
 

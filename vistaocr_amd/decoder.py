@@ -94,10 +94,8 @@ class BeamDecoder:
         key = str(dev)
         if key not in self._canon:
             self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
-        lens = batch_actual_timesteps
-        if torch.is_tensor(lens):
-            lens = lens.detach().cpu()
-        labels, lengths, scores = ops.ctc_beam_search(model_output.detach(), [int(v) for v in lens], self._canon[key], self.beam, nbest,
+        labels, lengths, scores = ops.ctc_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key],
+                                                      self.beam, nbest,
                                                       self.lm.to(dev) if self.lm is not None else None, self.lm_weight,
                                                       self.insertion_bonus, self.prune_logp)
         return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
@@ -106,27 +104,84 @@ class BeamDecoder:
         """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; labels are canonical alphabet indices,
         acoustic the CTC log-probability of the labelling, lm the LM log-probability including </s> (0 without an LM)."""
         nbest = self.nbest if nbest is None else int(nbest)
-        labels, lengths, scores = self._search(model_output, batch_actual_timesteps, nbest)
-        out = []
-        for b in range(labels.shape[0]):
-            hyps = []
-            for q in range(nbest):
-                if not np.isfinite(scores[b, q, 0]):
-                    break
-                hyps.append(([int(v) for v in labels[b, q, :lengths[b, q]]], tuple(float(s) for s in scores[b, q])))
-            out.append(hyps)
-        return out
+        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest))
 
     def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
         """The best hypothesis of each line in decode_greedy's format: space-joined uxxxx tokens, converted to utf8 unless uxxxx."""
         if lang is not None:
             raise ValueError("BeamDecoder: one alphabet per decoder (lang is not supported)")
-        labels, lengths, scores = self._search(model_output, batch_actual_timesteps, 1)
-        idx_to_char = self.alphabet.idx_to_char
-        result = []
-        for b in range(labels.shape[0]):
-            n = int(lengths[b, 0]) if np.isfinite(scores[b, 0, 0]) else 0
-            result.append(" ".join(idx_to_char[int(k)] for k in labels[b, 0, :n]))
-        if uxxxx == False:  # noqa: E712  (decode_greedy's comparison)
-            result = [uxxxx_to_utf8(r) for r in result]
-        return result
+        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1), self.alphabet, uxxxx)
+
+
+def _line_lengths(batch_actual_timesteps):
+    lens = batch_actual_timesteps
+    if torch.is_tensor(lens):
+        lens = lens.detach().cpu()
+    return [int(v) for v in lens]
+
+
+def _nbest_lists(labels, lengths, scores):
+    """The beam searches' outputs (host arrays [B,nbest,T], [B,nbest], [B,nbest,3]) as per-line lists of (labels, scores), best
+    first, up to the first rank the search did not fill (total -inf)."""
+    out = []
+    for b in range(labels.shape[0]):
+        hyps = []
+        for q in range(labels.shape[1]):
+            if not np.isfinite(scores[b, q, 0]):
+                break
+            hyps.append(([int(v) for v in labels[b, q, :lengths[b, q]]], tuple(float(s) for s in scores[b, q])))
+        out.append(hyps)
+    return out
+
+
+def _best_strings(labels, lengths, scores, alphabet, uxxxx):
+    """Rank 0 of every line as space-joined uxxxx tokens (an unfilled rank: ""), converted to utf8 unless uxxxx."""
+    idx_to_char = alphabet.idx_to_char
+    result = []
+    for b in range(labels.shape[0]):
+        n = int(lengths[b, 0]) if np.isfinite(scores[b, 0, 0]) else 0
+        result.append(" ".join(idx_to_char[int(k)] for k in labels[b, 0, :n]))
+    if uxxxx == False:  # noqa: E712  (decode_greedy's comparison)
+        result = [uxxxx_to_utf8(r) for r in result]
+    return result
+
+
+class WordBeamDecoder:
+    """CTC prefix beam search on the GPU scored by a word n-gram with a lexicon (vocr_ctc_word_beam_search, WordNgramLM): the stand-in
+    for the reference's TLG.fst decode (decode_with_lm, src/decoder.py:11-109).  Hypotheses are ranked by ln P_ctc(y | x) +
+    lm_weight * ln P_lm(tokens of y, </s>) + word_bonus * |tokens of y|, the tokens those of form_tokenized_words.  Letter-words are
+    limited to the LM's lexicon; with `oov_penalty` (a ln penalty, None: closed vocabulary) any other word is scored as <unk> plus the
+    penalty.  Output formats as BeamDecoder's."""
+
+    def __init__(self, alphabet, lm, beam=16, nbest=1, lm_weight=0.8, word_bonus=0.0, oov_penalty=None):
+        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
+            raise ValueError("WordBeamDecoder: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (beam, nbest))
+        if lm.trie_next.shape[1] != len(alphabet):
+            raise ValueError("WordBeamDecoder: the LM was resolved for %d symbols, the alphabet has %d" % (lm.trie_next.shape[1], len(alphabet)))
+        self.alphabet, self.lm = alphabet, lm
+        self.beam, self.nbest = int(beam), int(nbest)
+        self.lm_weight, self.word_bonus = float(lm_weight), float(word_bonus)
+        self.oov_penalty = None if oov_penalty is None else float(oov_penalty)
+        self._canon = {}
+
+    def _search(self, model_output, batch_actual_timesteps, nbest):
+        dev = model_output.device
+        key = str(dev)
+        if key not in self._canon:
+            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        labels, lengths, scores = ops.ctc_word_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key],
+                                                           self.lm.to(dev), self.beam, nbest, self.lm_weight, self.word_bonus,
+                                                           self.oov_penalty)
+        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
+
+    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
+        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; lm is the word LM's log-probability of the
+        tokens including </s>.  A line whose every beam ends inside a word that cannot close has no hypothesis."""
+        nbest = self.nbest if nbest is None else int(nbest)
+        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest))
+
+    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
+        """The best hypothesis of each line in decode_greedy's format ("" for a line without one)."""
+        if lang is not None:
+            raise ValueError("WordBeamDecoder: one alphabet per decoder (lang is not supported)")
+        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1), self.alphabet, uxxxx)

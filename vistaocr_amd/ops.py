@@ -1291,3 +1291,55 @@ def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weig
     call("vocr_ctc_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), *lm_args, float(lm_weight),
          float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores), _p(ws), ws.numel() * 4, _stream())
     return labels, out_lens, scores
+
+
+_WORD_LM_INT = ("kind", "tok", "trie_next", "trie_tok", "off", "succ_tok", "succ_next", "back")
+_WORD_LM_FLOAT = ("trie_la", "succ_logp", "bow")
+
+
+def ctc_word_beam_search(logits, lens, canon, lm, beam=16, nbest=1, lm_weight=0.8, word_bonus=0.0, oov_penalty=None):
+    """CTC prefix beam search scored by a word n-gram with a lexicon (vocr_ctc_word_beam_search) over raw logits [T,B,V].  `lens` and
+    `canon` as for ctc_beam_search; `lm`: the device tables of a WordNgramLM (WordNgramLM.to(device)); `oov_penalty` None: closed
+    vocabulary (every letter-word is a lexicon word), else the ln penalty added to ln P(<unk>) for a word outside the lexicon.
+    Returns (labels int32 [B,nbest,T], lengths int32 [B,nbest], scores fp32 [B,nbest,3] = total, acoustic, LM), on the device."""
+    _need_gpu(logits)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    dev = logits.device
+    lib = _lib.load()
+    nbytes = lib.vocr_ctc_word_beam_workspace_bytes(T, B, V, int(beam), int(nbest))
+    if nbytes == 0:
+        raise RuntimeError("ctc_word_beam_search: unsupported shape or beam (T=%d B=%d V=%d beam=%d nbest=%d; V <= 256, 1 <= nbest <= "
+                           "beam <= 128)" % (T, B, V, beam, nbest))
+    if torch.is_tensor(lens):
+        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    if lens_dev.numel() != B:
+        raise RuntimeError("ctc_word_beam_search: %d lengths for %d lines" % (lens_dev.numel(), B))
+    if canon is not None:
+        _need_gpu(canon)
+        if canon.dtype != torch.int32 or canon.numel() != V:
+            raise RuntimeError("ctc_word_beam_search: canon must be int32 [V]")
+    tabs = [lm[k] for k in _WORD_LM_INT + _WORD_LM_FLOAT]
+    _need_gpu(*tabs)
+    bad = [k for k in _WORD_LM_INT if lm[k].dtype != torch.int32 or not lm[k].is_contiguous()]
+    bad += [k for k in _WORD_LM_FLOAT if lm[k].dtype != torch.float32 or not lm[k].is_contiguous()]
+    Nn, S, E = lm["trie_tok"].numel(), lm["bow"].numel(), lm["succ_tok"].numel()
+    W = int(lm["num_tokens"])
+    if (bad or lm["kind"].numel() != V or lm["tok"].numel() != V or tuple(lm["trie_next"].shape) != (Nn, V) or lm["trie_la"].numel() != Nn
+            or lm["off"].numel() != S + 1 or lm["back"].numel() != S or lm["succ_logp"].numel() != E or lm["succ_next"].numel() != E
+            or not 1 <= W <= E):
+        raise RuntimeError("ctc_word_beam_search: word LM tables do not match V=%d (bad dtype or layout: %s; kind %s, trie_next %s, "
+                           "off %s, bow %s, succ_tok %s)" % (V, bad, tuple(lm["kind"].shape), tuple(lm["trie_next"].shape),
+                                                             tuple(lm["off"].shape), tuple(lm["bow"].shape), tuple(lm["succ_tok"].shape)))
+    labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    oov = float("-inf") if oov_penalty is None else float(oov_penalty)
+    call("vocr_ctc_word_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(lm["kind"]), _p(lm["tok"]),
+         _p(lm["trie_next"]), _p(lm["trie_tok"]), _p(lm["trie_la"]), Nn, _p(lm["off"]), _p(lm["succ_tok"]), _p(lm["succ_logp"]),
+         _p(lm["succ_next"]), _p(lm["bow"]), _p(lm["back"]), S, E, W, int(lm["start"]), int(lm["unk"]), int(lm["eos"]),
+         float(lm_weight), float(word_bonus), oov, _p(labels), _p(out_lens), _p(scores), _p(ws), ws.numel() * 4, _stream())
+    return labels, out_lens, scores
