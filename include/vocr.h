@@ -77,6 +77,11 @@ int vocr_conv3x3_wgrad(const float* x, const float* dy, float* dw, void* workspa
 int vocr_conv3x3_wino_supported(int cin, int cout);
 size_t vocr_conv3x3_wino_pack_floats(int cout, int cin);
 int vocr_conv3x3_wino_pack_weights(const float* w, float* wpack_fwd, float* wpack_dgrad, int cout, int cin, void* stream);
+/* which kernel vocr_conv3x3_wino_fwd takes for a launch (0: shape refused).  1 / 2 = F(2,3), 64 / 128 output channels per workgroup;
+ * F(4,3): 3 / 4 = one 4-wave workgroup per CU, 5 / 6 = one 8-wave workgroup, 7 / 8 = two 4-wave workgroups per CU (64 / 128 channels);
+ * 9 / 10 = the round-3 F(2,3) kernels (tensors of 2^29 elements or more).  +16: the last partial round of tiles is cut into direct-form
+ * tail pieces that lead the launch.  A data gradient is the launch vocr_conv3x3_wino_plan(n, cout, h, w, cin). */
+int vocr_conv3x3_wino_plan(int n, int cin, int h, int w, int cout);
 int vocr_conv3x3_wino_fwd(const float* x, const float* wpack, const float* bias, float* y,
                           int n, int cin, int h, int w, int cout, void* stream);
 /* Weight gradient with the transposed minimal-filtering transform F(3,2) along the row and - when cin * cout is a multiple of 4 -

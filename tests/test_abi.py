@@ -115,6 +115,11 @@ def test_argument_validation_without_gpu():
     assert lib.vocr_gather_rows_fill_grad(one, None, 4, 8, one, one, None) == -1
     assert lib.vocr_conv3x3_h16_plan(32, 64, 30, 600, 64) == 1 and lib.vocr_conv3x3_h16_plan(32, 24, 30, 600, 64) == 0
     assert lib.vocr_conv3x3_h16_plan(32, 128, 15, 420, 128) in (2, 3, 4, 5)
+    # the minimal-filtering launch plan (256 CUs without a device): F(2,3) below 64 output channels, two 4-wave F(4,3) workgroups per CU
+    # with tail pieces for configs[1]'s 64 -> 64 layer, eight waves for its 128 -> 64 data gradient; 0 for a shape the launcher refuses
+    assert lib.vocr_conv3x3_wino_plan(1, 8, 3, 33, 16) == 1 and lib.vocr_conv3x3_wino_plan(32, 64, 30, 600, 64) == 16 + 7
+    assert lib.vocr_conv3x3_wino_plan(32, 128, 15, 420, 64) == 5 and lib.vocr_conv3x3_wino_plan(32, 64, 15, 420, 128) == 8
+    assert lib.vocr_conv3x3_wino_plan(1, 8, 3, 33, 18) == 0 and lib.vocr_conv3x3_wino_plan(0, 8, 3, 33, 16) == 0
     # bf16x6 GEMM: plane sizes (rows padded to 256, K to 32; three planes of bf16) and argument validation
     assert lib.vocr_gemm_x6_planes_bytes(9408, 1024) == 3 * (37 * 8) * (32 * 2) * 1024 and lib.vocr_gemm_x6_planes_bytes(0, 8) == 0
     assert lib.vocr_gemm_x6_workspace_bytes(4096, 1024, 9408) > 0

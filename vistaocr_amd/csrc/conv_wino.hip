@@ -1624,42 +1624,35 @@ extern "C" int vocr_conv3x3_wino_pack_weights(const float* w, float* wpack_fwd, 
     return rc;
 }
 
-extern "C" int vocr_conv3x3_wino_fwd(const float* x, const float* wpack, const float* bias, float* y, int n, int cin, int h,
-                                     int w, int cout, void* stream) {
-    VOCR_CHECK_ARG(x && wpack && y, "vocr_conv3x3_wino_fwd: null pointer");
-    VOCR_CHECK_ARG(n > 0 && cin > 0 && h > 0 && w > 0 && cout > 0, "vocr_conv3x3_wino_fwd: bad shape");
-    VOCR_CHECK_ARG(cout % 4 == 0 && ((((uintptr_t)wpack) & 15) == 0), "vocr_conv3x3_wino_fwd: needs Cout %% 4 == 0 and a 16-byte aligned pack");
-    VOCR_CHECK_ARG((long)n * (cin > cout ? cin : cout) * h * w < (1l << 31), "vocr_conv3x3_wino_fwd: tensor exceeds 2^31 elements");
+namespace {
+// The kernel vocr_conv3x3_wino_fwd launches for a shape (vocr_conv3x3_wino_plan reports it: include/vocr.h) and how its grid splits into
+// direct-form tail pieces that lead the launch and whole tiles.  One rule for the launcher and the query, so the two cannot drift.
+enum WinoKind { WK_F23_64 = 1, WK_F23_128, WK_W4_64, WK_W4_128, WK_W8_64, WK_W8_128, WK_X2_64, WK_X2_128, WK_R3_64, WK_R3_128 };
+struct WinoPlan { int kind, n_tail, n_main; WGeom geo; };
+
+int wino_cu_count() {
+    int ncu = 256, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
+    return ncu;
+}
+
+// kind 0: a shape the launcher refuses (bad shape, Cout % 4 != 0, a tensor beyond the kernels' offsets)
+WinoPlan wino_plan_of(int n, int cin, int h, int w, int cout, int ncu) {
+    WinoPlan p = {0, 0, 0, {}};
+    if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0 || cout % 4 != 0) return p;
+    const long big = (long)n * (cin > cout ? cin : cout) * h * w;
+    if (big >= (1l << 31)) return p;
     const bool f43 = wino4_for(cout);
-    VOCR_CHECK_ARG(!f43 || (long)n * (cin > cout ? cin : cout) * h * w < (1l << 29), "vocr_conv3x3_wino_fwd: the F(4,3) kernel needs tensors below 2^29 elements");
-    WGeom geo;
+    if (f43 && big >= (1l << 29)) return p;
+    WGeom& geo = p.geo;
     geo.T = vocr_cdiv(w, f43 ? 4 : 2);
     geo.S = geo.T + 1;
     geo.slots_img = h * geo.S;
     geo.nslot = n * geo.slots_img;
     geo.nseg = vocr_cdiv(geo.nslot, TS);
-    const float* zp = wino_zero_page_ptr();
-    VOCR_CHECK_ARG(zp != nullptr, "vocr_conv3x3_wino_fwd: no device zero page");
-    hipStream_t s = (hipStream_t)stream;
-    const float* wdirect = wpack + (size_t)cin * (f43 ? 18 : 12) * cout;
     // VOCR_CONV_TAIL: 1 (default) the last partial round of tiles is cut into direct-form pieces that lead the launch, 0 whole tiles only
     static const int tail_mode = VOCR_EXPERIMENT_INT("VOCR_CONV_TAIL", 1);
-    int ncu = 256;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
-    }
-#define VOCR_WINO_LAUNCH(KERNEL, THREADS, CO_T, NSEG, CO_TILES)                                                             \
-    do {                                                                                                                    \
-        const int tiles = vocr_cdiv(geo.nseg, NSEG) * (CO_TILES), rem = tiles % ncu;                                        \
-        /* a piece is 1/16 of a tile in the direct form (1.5x the multiplications) and latency-bound when K is short:   */  \
-        /* measured worth it up to a quarter round of tiles, up to half a round from 128 input channels on               */  \
-        const bool cut = tail_mode == 1 && tiles > ncu && rem > 0 && (rem <= ncu / 4 || (rem <= ncu / 2 && cin >= 128));   \
-        const int n_main = cut ? tiles - rem : tiles, n_tail = cut ? rem * (CO_T / 32) * 2 * NSEG : 0;                      \
-        KERNEL<<<dim3(n_tail + n_main), THREADS, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, (CO_TILES), wdirect, n_tail, n_main); \
-    } while (0)
-    const int wino2 = wino2_mode();
     if (f43) {
         // one 4-wave workgroup per CU; a piece of the tail is 1/(CO_T/32 * 4 NSEG) of a tile
         // eight waves (two per SIMD, 128 channels x 4 segments per workgroup) unless that leaves CUs without a workgroup: then four waves
@@ -1674,27 +1667,60 @@ extern "C" int vocr_conv3x3_wino_fwd(const float* x, const float* wpack, const f
         const int slots4 = x2 ? 2 * ncu : ncu;              // workgroups resident at a time
         const int rem4 = tiles4 % slots4;
         const bool cut4 = tail_mode == 1 && tiles4 > slots4 && rem4 > 0 && rem4 <= slots4 / 2;
-        const int n_main4 = cut4 ? tiles4 - rem4 : tiles4;
+        p.n_main = cut4 ? tiles4 - rem4 : tiles4;
         // pieces per tile as conv3x3_wino4_body decodes them: COSUB x 4 x NSEG = 4 x 4 x nw/2 (128 channels) = 2 x 4 x nw (64) = 8 nw
         // (round 4 launched 16 nw: the second half mapped beyond the tiles and returned at once, each holding 61 - 126 KB of LDS)
-        const int n_tail4 = cut4 ? rem4 * 8 * nw : 0;
-        if (cout > 64) {
-            if (x2) conv3x3_wino4x2_kernel_128<<<dim3(n_tail4 + n_main4), 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, vocr_cdiv(cout, 128), wdirect, n_tail4, n_main4);
-            else if (nw == 8) conv3x3_wino4w8_kernel_128<<<dim3(n_tail4 + n_main4), 512, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, vocr_cdiv(cout, 128), wdirect, n_tail4, n_main4);
-            else conv3x3_wino4_kernel_128<<<dim3(n_tail4 + n_main4), 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, vocr_cdiv(cout, 128), wdirect, n_tail4, n_main4);
-        } else {
-            if (x2) conv3x3_wino4x2_kernel_64<<<dim3(n_tail4 + n_main4), 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, n_tail4, n_main4);
-            else if (nw == 8) conv3x3_wino4w8_kernel_64<<<dim3(n_tail4 + n_main4), 512, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, n_tail4, n_main4);
-            else conv3x3_wino4_kernel_64<<<dim3(n_tail4 + n_main4), 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, n_tail4, n_main4);
-        }
-    } else if (wino2 && (long)n * (cin > cout ? cin : cout) * h * w < (1l << 29)) {
-        if (cout > 64) VOCR_WINO_LAUNCH(conv3x3_wino2_kernel_128, 256, 128, 2, vocr_cdiv(cout, 128));
-        else VOCR_WINO_LAUNCH(conv3x3_wino2_kernel_64, 256, 64, 4, 1);
-    } else {
-        if (cout > 64) VOCR_WINO_LAUNCH(conv3x3_wino_kernel<128>, 256, 128, 2, vocr_cdiv(cout, 128));
-        else VOCR_WINO_LAUNCH(conv3x3_wino_kernel<64>, 256, 64, 4, 1);
+        p.n_tail = cut4 ? rem4 * 8 * nw : 0;
+        p.kind = x2 ? (cout > 64 ? WK_X2_128 : WK_X2_64) : nw == 8 ? (cout > 64 ? WK_W8_128 : WK_W8_64) : (cout > 64 ? WK_W4_128 : WK_W4_64);
+        return p;
     }
-#undef VOCR_WINO_LAUNCH
+    const bool f23 = wino2_mode() && big < (1l << 29);
+    p.kind = cout > 64 ? (f23 ? WK_F23_128 : WK_R3_128) : (f23 ? WK_F23_64 : WK_R3_64);
+    // 128 output channels x 2 segments or 64 x 4 per tile; a piece is 1/16 of a tile in the direct form (1.5x the multiplications) and
+    // latency-bound when K is short: measured worth it up to a quarter round of tiles, up to half a round from 128 input channels on
+    const int co_t = cout > 64 ? 128 : 64, nseg_t = cout > 64 ? 2 : 4, co_tiles = cout > 64 ? vocr_cdiv(cout, 128) : 1;
+    const int tiles = vocr_cdiv(geo.nseg, nseg_t) * co_tiles, rem = tiles % ncu;
+    const bool cut = tail_mode == 1 && tiles > ncu && rem > 0 && (rem <= ncu / 4 || (rem <= ncu / 2 && cin >= 128));
+    p.n_main = cut ? tiles - rem : tiles;
+    p.n_tail = cut ? rem * (co_t / 32) * 2 * nseg_t : 0;
+    return p;
+}
+}  // namespace
+
+extern "C" int vocr_conv3x3_wino_plan(int n, int cin, int h, int w, int cout) {
+    const WinoPlan p = wino_plan_of(n, cin, h, w, cout, wino_cu_count());
+    return p.kind == 0 ? 0 : p.kind + (p.n_tail > 0 ? 16 : 0);
+}
+
+extern "C" int vocr_conv3x3_wino_fwd(const float* x, const float* wpack, const float* bias, float* y, int n, int cin, int h,
+                                     int w, int cout, void* stream) {
+    VOCR_CHECK_ARG(x && wpack && y, "vocr_conv3x3_wino_fwd: null pointer");
+    VOCR_CHECK_ARG(n > 0 && cin > 0 && h > 0 && w > 0 && cout > 0, "vocr_conv3x3_wino_fwd: bad shape");
+    VOCR_CHECK_ARG(cout % 4 == 0 && ((((uintptr_t)wpack) & 15) == 0), "vocr_conv3x3_wino_fwd: needs Cout %% 4 == 0 and a 16-byte aligned pack");
+    VOCR_CHECK_ARG((long)n * (cin > cout ? cin : cout) * h * w < (1l << 31), "vocr_conv3x3_wino_fwd: tensor exceeds 2^31 elements");
+    const bool f43 = wino4_for(cout);
+    VOCR_CHECK_ARG(!f43 || (long)n * (cin > cout ? cin : cout) * h * w < (1l << 29), "vocr_conv3x3_wino_fwd: the F(4,3) kernel needs tensors below 2^29 elements");
+    const WinoPlan p = wino_plan_of(n, cin, h, w, cout, wino_cu_count());
+    VOCR_CHECK_ARG(p.kind != 0, "vocr_conv3x3_wino_fwd: no kernel for this shape");
+    const WGeom geo = p.geo;
+    const float* zp = wino_zero_page_ptr();
+    VOCR_CHECK_ARG(zp != nullptr, "vocr_conv3x3_wino_fwd: no device zero page");
+    hipStream_t s = (hipStream_t)stream;
+    const float* wdirect = wpack + (size_t)cin * (f43 ? 18 : 12) * cout;
+    const dim3 grid(p.n_tail + p.n_main);
+    const int ct = vocr_cdiv(cout, 128);
+    switch (p.kind) {
+        case WK_X2_128: conv3x3_wino4x2_kernel_128<<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, ct, wdirect, p.n_tail, p.n_main); break;
+        case WK_W8_128: conv3x3_wino4w8_kernel_128<<<grid, 512, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, ct, wdirect, p.n_tail, p.n_main); break;
+        case WK_W4_128: conv3x3_wino4_kernel_128<<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, ct, wdirect, p.n_tail, p.n_main); break;
+        case WK_X2_64: conv3x3_wino4x2_kernel_64<<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, p.n_tail, p.n_main); break;
+        case WK_W8_64: conv3x3_wino4w8_kernel_64<<<grid, 512, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, p.n_tail, p.n_main); break;
+        case WK_W4_64: conv3x3_wino4_kernel_64<<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, p.n_tail, p.n_main); break;
+        case WK_F23_128: conv3x3_wino2_kernel_128<<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, ct, wdirect, p.n_tail, p.n_main); break;
+        case WK_F23_64: conv3x3_wino2_kernel_64<<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, p.n_tail, p.n_main); break;
+        case WK_R3_128: conv3x3_wino_kernel<128><<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, ct, wdirect, p.n_tail, p.n_main); break;
+        default: conv3x3_wino_kernel<64><<<grid, 256, 0, s>>>(x, wpack, bias, y, zp, n, cin, h, w, cout, geo, 1, wdirect, p.n_tail, p.n_main); break;
+    }
     VOCR_CHECK_LAUNCH("vocr_conv3x3_wino_fwd");
     return VOCR_OK;
 }
