@@ -464,6 +464,30 @@ int vocr_ctc_word_beam_search(const float* logits, const int32_t* lens, int t, i
                               float word_bonus, float oov_penalty, int32_t* out_labels, int32_t* out_lens, float* out_scores,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC forced alignment: conf_utils.form_confidence_gt of src/conf_test.py (a module the reference never shipped) ---- */
+/* The best (Viterbi) CTC path of a KNOWN labelling through the frames, the frame span of every label on it, per-label scores, and the
+ * forward score of the labelling from the same sweep: what per-character positions and confidences are made of.  One independent
+ * problem per (line b, hypothesis q).  logits[T][B][V] raw (log-softmax inside), lens[B] device int32 (clamped to [0, T]), canon[V]
+ * as for vocr_ctc_beam_search (NULL: identity): a class's log-probability is the logsumexp of its member columns and a label given
+ * as any member index stands for its class.  labels[B][n][label_stride], label_lens[B][n] device int32: the layout the beam searches
+ * write (n = nbest, label_stride = T); a greedy or ground-truth transcript packs as n = 1.  Blank = 0, S = 2L+1 extended positions,
+ * the skip s-2 -> s allowed iff position s is not blank and its class differs from that of s-2 (vocr_ctc_loss_grad's rule).
+ * Viterbi tie rule: among equal predecessors prefer s, then s-1, then s-2; at the last frame the final blank 2L wins over 2L-1.
+ * Outputs: out_scores[B][n][2] = {ln P(best path), ln P_ctc(labels | x)}; out_spans[B][n][max_label_len][2] = {first, last} frame
+ * (inclusive) of label p, -1 for p >= L and on lines without an alignment; out_label_scores[B][n][max_label_len][2] = {peak, sum}
+ * of the class's frame log-probability over the span (0 where the span is -1; mean = sum / span length).  L = 0: both scores are
+ * the sum of ln p_t(blank) (0 when lens[b] = 0).  Both scores -inf and every span -1: a labelling that does not fit the frames or
+ * uses a class the frames give -inf, a label <= 0 or >= v or in the blank's class, label_lens > max_label_len.  -inf logits are
+ * legal and never yield NaN.  Results are bit-identical from run to run.  Limits: 2 <= v <= 256, 1 <= n <= 128,
+ * 0 <= max_label_len <= t, label_stride >= max_label_len, any t the beam searches take (t * b * n < 2^31).  Workspace (the class
+ * log-probabilities; the back pointers where they do not fit the LDS; beyond 1663 labels also the rows of the sweep) from
+ * vocr_ctc_align_workspace_bytes (0 for an unsupported shape); an unsupported shape fails with VOCR_EINVAL before any launch. */
+size_t vocr_ctc_align_workspace_bytes(int t, int b, int v, int n, int max_label_len);
+int vocr_ctc_align(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                   const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
+                   float* out_scores, int32_t* out_spans, float* out_label_scores,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

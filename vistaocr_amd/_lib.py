@@ -111,6 +111,8 @@ SIGNATURES = {
     "vocr_ctc_word_beam_workspace_bytes": (Z, [I, I, I, I, I]),
     "vocr_ctc_word_beam_search": (I, [P, P, I, I, I, P, I, I, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, I, F, F, F, P, P, P, P,
                                       Z, P]),
+    "vocr_ctc_align_workspace_bytes": (Z, [I, I, I, I, I]),
+    "vocr_ctc_align": (I, [P, P, I, I, I, P, P, P, I, I, I, P, P, P, P, Z, P]),
     "vocr_clamp_adam": (I, [P, P, P, P, Z, F, F, F, F, F, F, F, I, P, P]),
     "vocr_clamp": (I, [P, Z, F, P, P]),
     "vocr_comm_unique_id": (I, [P]),

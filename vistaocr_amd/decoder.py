@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .align import lines_from_arrays, one_copy
 from .textutils import uxxxx_to_utf8
 
 
@@ -72,6 +73,19 @@ class ArgmaxDecoder:
         alphabet = self.alphabet if lang is None else self.alphabet[lang]
         return decode_greedy(model_output, batch_actual_timesteps, alphabet, uxxxx=uxxxx)
 
+    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
+        """(hypotheses as decode() returns them, per line a LineAlignment of that hypothesis: vistaocr_amd.align).  The collapse runs on
+        the device (vocr_greedy_collapse) and its labels go to vocr_ctc_align without leaving it; one device-to-host copy at the end."""
+        alphabet = self.alphabet if lang is None else self.alphabet[lang]
+        dev = model_output.device
+        lens = _line_lengths(batch_actual_timesteps)
+        idx, mx = ops.argmax_rows(model_output.detach())
+        lens_dev = torch.as_tensor(lens, dtype=torch.int32).to(dev)
+        canon = torch.as_tensor(alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        labels, counts = ops.greedy_collapse(idx, mx, lens_dev, canon, np.float32(3 * 1 / len(alphabet)))
+        labels, counts = labels.unsqueeze(1), counts.unsqueeze(1)
+        return _aligned(model_output, lens_dev, labels, counts, None, canon, alphabet, uxxxx, 1)
+
 
 class BeamDecoder:
     """CTC prefix beam search on the GPU (vocr_ctc_beam_search), optionally with a character n-gram LM (vistaocr_amd.lm.CharNgramLM):
@@ -89,16 +103,28 @@ class BeamDecoder:
         self.lm, self.lm_weight, self.insertion_bonus, self.prune_logp = lm, float(lm_weight), float(insertion_bonus), prune_logp
         self._canon = {}
 
-    def _search(self, model_output, batch_actual_timesteps, nbest):
+    def _search_device(self, model_output, batch_actual_timesteps, nbest):
         dev = model_output.device
         key = str(dev)
         if key not in self._canon:
             self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
-        labels, lengths, scores = ops.ctc_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key],
-                                                      self.beam, nbest,
-                                                      self.lm.to(dev) if self.lm is not None else None, self.lm_weight,
-                                                      self.insertion_bonus, self.prune_logp)
+        return ops.ctc_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key], self.beam, nbest,
+                                   self.lm.to(dev) if self.lm is not None else None, self.lm_weight, self.insertion_bonus,
+                                   self.prune_logp)
+
+    def _search(self, model_output, batch_actual_timesteps, nbest):
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest)
         return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
+
+    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1):
+        """(hypotheses as decode() returns them, alignments): the search, then vocr_ctc_align on its device outputs, one device-to-host
+        copy at the end.  nbest = 1: per line the LineAlignment (vistaocr_amd.align) of the best hypothesis, None where the search
+        found none.  nbest > 1: per line a list of (labels, (total, acoustic, lm), LineAlignment), best first, as decode_nbest lists
+        them.  An alignment's ctc_logp is the full forward score of the labelling; the search's acoustic score sums only the paths its
+        beam kept, so it is a lower bound of it and equals it when the beam pruned nothing of weight."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest))
+        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
 
     def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
         """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; labels are canonical alphabet indices,
@@ -118,6 +144,21 @@ def _line_lengths(batch_actual_timesteps):
     if torch.is_tensor(lens):
         lens = lens.detach().cpu()
     return [int(v) for v in lens]
+
+
+def _aligned(model_output, lens, labels, lengths, scores, canon, alphabet, uxxxx, nbest):
+    """decode_aligned's common end: align the device labellings [B,n,T] / [B,n] (scores [B,n,3] or None: every rank is a hypothesis),
+    copy everything to the host once, format."""
+    a_scores, spans, lsc = ops.ctc_align(model_output.detach(), lens, labels, lengths, canon)
+    if scores is None:
+        scores = torch.zeros(labels.shape[0], labels.shape[1], 3, dtype=torch.float32, device=labels.device)
+    labels, lengths, scores, a_scores, spans, lsc = one_copy([labels, lengths, scores, a_scores, spans, lsc])
+    rows = lines_from_arrays(labels, lengths, a_scores, spans, lsc, alphabet)
+    hyps = _best_strings(labels, lengths, scores, alphabet, uxxxx)
+    if nbest == 1:
+        return hyps, [row[0] if np.isfinite(scores[b, 0, 0]) else None for b, row in enumerate(rows)]
+    lists = _nbest_lists(labels, lengths, scores)
+    return hyps, [[(h[0], h[1], row[q]) for q, h in enumerate(lst)] for lst, row in zip(lists, rows)]
 
 
 def _nbest_lists(labels, lengths, scores):
@@ -164,15 +205,23 @@ class WordBeamDecoder:
         self.oov_penalty = None if oov_penalty is None else float(oov_penalty)
         self._canon = {}
 
-    def _search(self, model_output, batch_actual_timesteps, nbest):
+    def _search_device(self, model_output, batch_actual_timesteps, nbest):
         dev = model_output.device
         key = str(dev)
         if key not in self._canon:
             self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
-        labels, lengths, scores = ops.ctc_word_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key],
-                                                           self.lm.to(dev), self.beam, nbest, self.lm_weight, self.word_bonus,
-                                                           self.oov_penalty)
+        return ops.ctc_word_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key], self.lm.to(dev),
+                                        self.beam, nbest, self.lm_weight, self.word_bonus, self.oov_penalty)
+
+    def _search(self, model_output, batch_actual_timesteps, nbest):
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest)
         return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
+
+    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1):
+        """BeamDecoder.decode_aligned for the word search: (hypotheses, alignments)."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest))
+        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
 
     def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
         """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; lm is the word LM's log-probability of the

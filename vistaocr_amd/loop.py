@@ -246,7 +246,7 @@ def _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataload
     return hist
 
 
-def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None):
+def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None, aligner=None):
     """The inference driver of src/decode_testset.py:42-206 without the LM branch: forward every batch, greedy-decode,
     and write `hyp-chars.txt` ("<uxxxx ...> (<utt-id>)") and `hyp-chars.txt.utf8` ("<utf8> (<utt-id minus last _part>)").
     The reference runs the decode in a background process because its per-frame numpy argmax is slow; here the argmax
@@ -254,20 +254,37 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     (`utf8_visual_to_logical`, src/textutils.py:186-212; identity for left-to-right scripts).  Seeds like the reference
     (FractionalMaxPool draws samples in eval too, decode_testset.py:70-71).  `decoder`: an object with the ArgmaxDecoder /
     BeamDecoder `.decode(model_output, lens, uxxxx=False)` interface that produces the hypotheses instead of the greedy decode
-    (None: the greedy decode); the files have the same format either way.  Returns the number of lines written."""
+    (None: the greedy decode); the files have the same format either way.  `aligner`: a vistaocr_amd.CtcAligner; with one, every
+    hypothesis is aligned to its frames and `hyp-words.tsv` is written as well, one row per token of form_tokenized_words:
+    utt-id, token (uxxxx, characters joined by "_"), x0, x1 (input pixels, CtcAligner.pixel_spans: good to about one frame width),
+    min_conf, mean_logp, tab-separated, in the decoder's (visual) order.  Without one (the default) exactly the two files above are
+    written.  Returns the number of lines written."""
+    import contextlib
     import os
-    from .textutils import utf8_to_uxxxx
+    from .textutils import utf8_to_uxxxx, uxxxx_to_utf8
     torch.manual_seed(seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(seed)
     os.makedirs(outdir, exist_ok=True)
     model.eval()
     n = 0
+    words_file = open(os.path.join(outdir, "hyp-words.tsv"), "w") if aligner is not None else contextlib.nullcontext()
     with torch.no_grad(), open(os.path.join(outdir, "hyp-chars.txt"), "w") as fh, \
-            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8:
+            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw:
         for x, _target, widths, _target_lens, meta in dataloader:
             out, lens = model(x.cuda(non_blocking=True), widths)
-            hyps = model.decode_without_lm(out, lens, uxxxx=False) if decoder is None else decoder.decode(out, lens, uxxxx=False)
+            if aligner is None:
+                hyps = model.decode_without_lm(out, lens, uxxxx=False) if decoder is None else decoder.decode(out, lens, uxxxx=False)
+            else:
+                # the same hypotheses in uxxxx form (decode's utf8 is uxxxx_to_utf8 of them), aligned as they stand
+                hyps_ux = model.decode_without_lm(out, lens, uxxxx=True) if decoder is None else decoder.decode(out, lens, uxxxx=True)
+                hyps = [uxxxx_to_utf8(h) for h in hyps_ux]
+                for i, al in enumerate(aligner.align(out, lens, hyps_ux)):
+                    if al is None:
+                        continue
+                    words = aligner.words(al)
+                    for w, (x0, x1) in zip(words, aligner.pixel_spans(words, int(widths[i]), int(lens[i]))):
+                        fhw.write("%s\t%s\t%d\t%d\t%.6f\t%.6f\n" % (meta["utt-ids"][i], w.token, x0, x1, w.min_conf, w.mean_logp))
             for i, hyp in enumerate(hyps):
                 hyp_utf8 = visual_to_logical(hyp) if visual_to_logical is not None else hyp
                 uttid = meta["utt-ids"][i]
