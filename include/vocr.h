@@ -488,6 +488,30 @@ int vocr_ctc_align(const float* logits, const int32_t* lens, int t, int b, int v
                    float* out_scores, int32_t* out_spans, float* out_label_scores,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC edit scores: eesen's lattice (lattice_beam of init_lm) and the confidence experiment of src/conf_test.py ---- */
+/* The exact CTC forward score of EVERY labelling one edit away from a hypothesis: what a per-character posterior, ranked alternatives
+ * and a "something is missing here" signal are made of.  Inputs, classes, blank, transition rule and the (line b, hypothesis q)
+ * layout are vocr_ctc_align's.  Outputs, fp32 natural log, M = max_label_len, L = label_lens[b][q]:
+ *   out_ctc[B][n]         ln P_ctc(labels | x) (vocr_ctc_align's second score);
+ *   out_sub[B][n][M][V]   at [p][c] the score of the labelling with label p replaced by the class of column c: columns of one class
+ *                         hold the same bits, column 0 and every column of the blank's class hold -inf, the column of the label's
+ *                         own class holds the unedited score (from the edit's own sum: equal to out_ctc up to rounding);
+ *   out_del[B][n][M]      the score with label p removed;
+ *   out_ins[B][n][M+1][V] at [q][c] the score with the class of column c inserted before label q (q = L appends);
+ * entries at p >= L or q > L are -inf.  Every entry is the forward score of the edited labelling with no special case: a hypothesis
+ * that does not fit its frames still has finite deletion scores where the shortened labelling fits, and with lens[b] = 0 the
+ * deletion of an only label scores 0.  A labelling with a label <= 0 or >= v or in the blank's class, or label_lens outside
+ * [0, M], gives -inf everywhere.  -inf logits are legal and never yield NaN.  Results are bit-identical from run to run.
+ * Limits: 2 <= v <= 256, 1 <= n <= 128, 0 <= max_label_len <= t, label_stride >= max_label_len, t * b * n < 2^31, the forward and
+ * backward lattices of all labellings (b * n * 8 * t * (2 * max_label_len + 1) bytes) at most 2 GiB, max_label_len <= 1823 (one row
+ * of the sweep in the LDS).  Workspace (the class log-probabilities and the lattices) from vocr_ctc_edit_workspace_bytes (0 for an
+ * unsupported shape); an unsupported shape fails with VOCR_EINVAL before any launch. */
+size_t vocr_ctc_edit_workspace_bytes(int t, int b, int v, int n, int max_label_len);
+int vocr_ctc_edit_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                         const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
+                         float* out_ctc, float* out_sub, float* out_del, float* out_ins,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

@@ -1,0 +1,362 @@
+// CTC edit scores: the exact CTC forward score ln P_ctc(labelling' | x) of EVERY labelling one edit away from a hypothesis - each
+// substitution of one label by another class, each deletion, each insertion of a class between two labels.  What a per-character
+// posterior, ranked alternatives and a "something is missing here" signal are made of (the reference got them from eesen's lattice and
+// the confidence experiment of src/conf_test.py).  Inputs and conventions are vocr_ctc_align's: blank = 0, extended sequence of
+// S = 2L+1 positions, the skip s-2 -> s iff position s is not blank and its CLASS differs from that of s-2, classes from canon[V].
+//
+// alpha[t][s] / beta[t][s] are the forward / backward lattices of the hypothesis (beta includes the emission at t).  alpha up to
+// position 2p and beta from position 2p+2 do not depend on label p, so an edit at p is a recursion over one or two NEW states between
+// them, x (the edited or inserted label) and y (the blank behind an inserted label):
+//   x(0) = lp(0,c) if p = 0 else -inf;   x(t) = lp(t,c) + lse(x(t-1), alpha[t-1][2p], alpha[t-1][2p-1] if p > 0 and c != l(p-1))
+//   y(0) = -inf;                         y(t) = lp(t,0) + lse(y(t-1), x(t-1))
+//   substitution p -> c : lse_t x(t) + e(t),  e(t) = lse(beta[t+1][2p+2], beta[t+1][2p+3] if p < L-1 and c != l(p+1)),
+//                         e(len-1) = 0 if p = L-1 else -inf
+//   deletion of p       : p = 0: lse(beta[0][2], beta[0][3] if L > 1);  else lse_t alpha[t][2p-1] + e(t), the skip iff l(p-1) != l(p+1)
+//   insertion of c at q : q < L: lse_t<len-1 of (x(t) + beta[t+1][2q+1] if c != l(q)) and y(t) + beta[t+1][2q+1];  q = L: x(len-1), y(len-1)
+// ("!=" compares classes).  Every sum cuts a path at its last frame in a given state, so no path is counted twice.
+//
+//   kernel 1  class log-probabilities : class_logprob_rows_kernel of the alignment, once per line.
+//   kernel 2  lattices                : one wave per (line, hypothesis, direction) writes alpha or beta to the workspace, TRANSPOSED
+//                                       ([s][t]: kernel 3 walks one position through the frames).  beta is alpha of the reversed
+//                                       labelling over the reversed frames, so both directions run the same code.  S <= 64: one
+//                                       position per lane, the row in registers, neighbours by shuffles, the gathered
+//                                       log-probabilities prefetched PF frames ahead.  S > 64: the row in LDS, lanes over 64-position
+//                                       chunks updated in place from the highest chunk down, TB frames of gathered log-probabilities
+//                                       staged per pass.  The forward wave also writes ln P_ctc(labels | x).
+//   kernel 3  edit scores             : one workgroup per (line, hypothesis, slot p), p = 0 .. max_label_len; thread c owns column c
+//                                       (coalesced class log-probabilities).  One pass over the frames serves the substitution at p,
+//                                       the insertion before p (the same x) and the deletion of p.  The alpha / beta values of a
+//                                       frame are the same for the whole workgroup and, like the column's own log-probability,
+//                                       are loaded PF frames ahead.  The sums over t are kept as (max, sum): one exponential per
+//                                       term and one logarithm at the end.  No LDS, no barrier.
+// Every float is computed by a fixed thread in a fixed order and the only cross-lane operations are shuffles and ballots: results are
+// bit-identical from run to run, and columns of one class (which read the same class log-probabilities) hold the same bits.
+#include "ctc_align_common.h"
+
+namespace {
+
+constexpr int PF = 8;                        // frames of loads in flight (kernel 2, S <= 64; kernel 3)
+constexpr int TB = 8;                        // kernel 2, S > 64: frames staged per gather pass
+constexpr size_t LDS_BUDGET = 144 * 1024;    // of the 160 KiB per CU
+constexpr size_t LATTICE_BYTES_MAX = (size_t)1 << 31;
+
+__device__ __forceinline__ float lse2(float a, float b) {
+    const float m = fmaxf(a, b);
+    if (m == NEG_INF) return NEG_INF;
+    return logf(expf(a - m) + expf(b - m)) + m;
+}
+
+// a labelling no edit of which is scored: bad length, a label outside (0, V) or in the blank's class.  Wave-uniform.
+__device__ __forceinline__ bool labelling_bad(const int32_t* __restrict__ canon, const int32_t* __restrict__ lab, int L, int V,
+                                              int max_label_len, int lane) {
+    if (L < 0 || L > max_label_len) return true;
+    bool mine = false;
+    for (int p = lane; p < L; p += 64) {
+        const int v = lab[p];
+        mine |= (v <= 0 || v >= V) || class_of(canon, min(max(v, 0), V - 1)) == 0;
+    }
+    return __any(mine);
+}
+
+// grid.x = B * n * 2 (direction fastest), 64 threads.  lat: [B * n][2][SM = 2 * max_label_len + 1][T] floats.  Dynamic LDS (S > 64 only):
+// the row with 2 leading -inf pads, ext[SP], the staged log-probabilities [TB][SP].
+__global__ __launch_bounds__(64) void ctc_edit_lattice_kernel(const float* __restrict__ clp, const int32_t* __restrict__ lens,
+                                                              const int32_t* __restrict__ canon, const int32_t* __restrict__ labels,
+                                                              const int32_t* __restrict__ label_lens, int T, int B, int V, int n,
+                                                              int label_stride, int max_label_len, int SP, float* __restrict__ lat,
+                                                              float* __restrict__ out_ctc) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = threadIdx.x;
+    const int prob = blockIdx.x >> 1, dir = blockIdx.x & 1, b = prob / n;
+    const int len = min(max(lens[b], 0), T);
+    const int L = label_lens[prob];
+    const int32_t* lab = labels + (long)prob * label_stride;
+    const long tstride = (long)B * V;
+    const float* lpb = clp + (long)b * V;                       // lpb[t * tstride + v]
+    const bool bad = labelling_bad(canon, lab, L, V, max_label_len, lane);
+    if (bad || len == 0) {                                      // kernel 3 reads no lattice of such a problem
+        if (dir == 0 && lane == 0) out_ctc[prob] = (!bad && L == 0) ? 0.f : NEG_INF;
+        return;
+    }
+    const int S = 2 * L + 1;
+    float* dst = lat + ((long)prob * 2 + dir) * (2 * max_label_len + 1) * T;
+    // backward: position s' of the reversed labelling at reversed frame t' is position S-1-s' at frame len-1-t'
+#define LABEL_AT(p) (dir ? lab[L - 1 - (p)] : lab[(p)])
+#define FRAME(t) (dir ? len - 1 - (t) : (t))
+#define POS(s) (dir ? S - 1 - (s) : (s))
+    float as, cs;                                               // the two end states of the last frame
+    if (S <= 64) {
+        const bool in = lane < S;
+        const int e = (in && (lane & 1)) ? LABEL_AT(lane >> 1) : 0;
+        const int c = class_of(canon, e);
+        const int c_m2 = __shfl_up(c, 2, 64);
+        const bool skip = lane >= 2 && e != 0 && c != c_m2;
+        const float* col = lpb + e;
+        float* out = dst + (long)POS(in ? lane : 0) * T;
+        float vs = NEG_INF;
+        if (lane == 0 || (lane == 1 && S > 1)) vs = col[(long)FRAME(0) * tstride];
+        if (in) out[FRAME(0)] = vs;
+        float buf[PF];
+#pragma unroll
+        for (int k = 0; k < PF; ++k) buf[k] = col[(long)FRAME(min(1 + k, len - 1)) * tstride];
+        for (int t0 = 1; t0 < len; t0 += PF) {
+#pragma unroll
+            for (int k = 0; k < PF; ++k) {
+                const int t = t0 + k;
+                if (t < len) {                                   // wave-uniform
+                    const float lpe = buf[k];
+                    buf[k] = col[(long)FRAME(min(t + PF, len - 1)) * tstride];
+                    float a2 = __shfl_up(vs, 1, 64), a3 = __shfl_up(vs, 2, 64);
+                    if (lane < 1) a2 = NEG_INF;
+                    if (!skip) a3 = NEG_INF;
+                    vs = in ? lse3(vs, a2, a3) + lpe : NEG_INF;
+                    if (in) out[FRAME(t)] = vs;
+                }
+            }
+        }
+        as = __shfl(vs, S - 1, 64);
+        cs = S > 1 ? __shfl(vs, S - 2, 64) : NEG_INF;
+    } else {
+        float* rs = sm;                                          // rs[2 + s]
+        int* ext = (int*)(sm + SP + 2);                          // label | class << 16
+        float* em = sm + SP + 2 + SP;                            // em[k * SP + s]
+        const int NC = (S + 63) >> 6;
+        for (int s = lane; s < S; s += 64) {
+            const int e = (s & 1) ? LABEL_AT(s >> 1) : 0;
+            ext[s] = e | (class_of(canon, e) << 16);
+            const float v = s < 2 ? lpb[(long)FRAME(0) * tstride + e] : NEG_INF;
+            rs[2 + s] = v;
+            dst[(long)POS(s) * T + FRAME(0)] = v;
+        }
+        if (lane < 2) rs[lane] = NEG_INF;
+        __syncthreads();
+        for (int t0 = 1; t0 < len; t0 += TB) {
+            const int nk = min(TB, len - t0);
+            for (int s = lane; s < S; s += 64) {
+                const float* col = lpb + (ext[s] & 0xffff);
+#pragma unroll
+                for (int k = 0; k < TB; ++k)
+                    if (k < nk) em[k * SP + s] = col[(long)FRAME(t0 + k) * tstride];
+            }
+            __syncthreads();
+            for (int k = 0; k < nk; ++k) {
+                const int ft = FRAME(t0 + k);
+                for (int ch = NC - 1; ch >= 0; --ch) {           // a chunk reads only positions that no earlier chunk of the step wrote
+                    const int s = ch * 64 + lane;
+                    const bool in = s < S;
+                    float ns = NEG_INF;
+                    if (in) {
+                        const int x = ext[s];
+                        const bool skip = s >= 2 && (x & 0xffff) != 0 && (x >> 16) != (ext[s - 2] >> 16);
+                        ns = lse3(rs[2 + s], rs[1 + s], skip ? rs[s] : NEG_INF) + em[k * SP + s];
+                    }
+                    __builtin_amdgcn_wave_barrier();             // every lane of the chunk has read before any writes
+                    if (in) {
+                        rs[2 + s] = ns;
+                        dst[(long)POS(s) * T + ft] = ns;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        as = rs[2 + S - 1];
+        cs = rs[2 + S - 2];
+    }
+#undef LABEL_AT
+#undef FRAME
+#undef POS
+    if (dir == 0 && lane == 0) out_ctc[prob] = lse2(as, cs);
+}
+
+// a logsumexp kept as (max, sum): one exponential per term
+struct LseAcc {
+    float m = NEG_INF, s = 0.f;
+    __device__ __forceinline__ void add(float v) {
+        if (v == NEG_INF) return;
+        const float e = expf(-fabsf(m - v));                     // m = -inf: 0
+        s = v > m ? s * e + 1.f : s + e;
+        m = fmaxf(m, v);
+    }
+    __device__ __forceinline__ float get() const { return m == NEG_INF ? NEG_INF : m + logf(s); }
+};
+
+// what kernel 3 needs of one frame t: the column's and the blank's class log-probability, alpha[t][2p], alpha[t][2p-1] and
+// beta[t+1][2p+1 .. 2p+3] (-inf where the position does not exist)
+struct EditFrame {
+    float lpc, lp0, a0, a1, b1, b2, b3;
+};
+
+// grid.x = B * n * (max_label_len + 1), V rounded up to 64 threads.
+__global__ __launch_bounds__(256) void ctc_edit_scores_kernel(const float* __restrict__ clp, const int32_t* __restrict__ lens,
+                                                              const int32_t* __restrict__ canon, const int32_t* __restrict__ labels,
+                                                              const int32_t* __restrict__ label_lens, int T, int B, int V, int n,
+                                                              int label_stride, int max_label_len, const float* __restrict__ lat,
+                                                              float* __restrict__ out_sub, float* __restrict__ out_del,
+                                                              float* __restrict__ out_ins) {
+    const int M = max_label_len;
+    const int prob = blockIdx.x / (M + 1), p = blockIdx.x - prob * (M + 1), b = prob / n;
+    const int c = threadIdx.x, cc = min(c, V - 1);
+    const int len = min(max(lens[b], 0), T);
+    const int L = label_lens[prob];
+    const int32_t* lab = labels + (long)prob * label_stride;
+    float* sub = p < M ? out_sub + ((long)prob * M + p) * V : nullptr;
+    float* del = p < M ? out_del + (long)prob * M + p : nullptr;
+    float* ins = out_ins + ((long)prob * (M + 1) + p) * V;
+    const bool bad = labelling_bad(canon, lab, L, V, M, threadIdx.x & 63);
+    if (bad || p > L || len == 0) {
+        if (c < V) {
+            ins[c] = NEG_INF;
+            if (sub) sub[c] = NEG_INF;
+        }
+        // no frames: the one labelling with a score is the empty one, which the deletion of an only label leaves
+        if (c == 0 && del) *del = (!bad && len == 0 && L == 1 && p == 0) ? 0.f : NEG_INF;
+        return;
+    }
+    const int cls_c = class_of(canon, cc);
+    const int cls_m1 = p > 0 ? class_of(canon, lab[p - 1]) : -1;
+    const int cls_0 = p < L ? class_of(canon, lab[p]) : -1;
+    const int cls_p1 = p < L - 1 ? class_of(canon, lab[p + 1]) : -1;
+    const bool skip_a = p > 0 && cls_c != cls_m1;                // x may be entered from label p-1
+    const bool skip_b = p < L - 1 && cls_c != cls_p1;            // a substituted x may leave to label p+1
+    const bool ins_x = p < L && cls_c != cls_0;                  // an inserted x may leave to label p
+    const bool skip_d = p > 0 && p < L - 1 && cls_m1 != cls_p1;  // label p-1 may leave to label p+1 once p is deleted
+    const long tstride = (long)B * V;
+    const float* lpb = clp + (long)b * V;
+    const long SM = 2 * (long)M + 1;
+    const float* alpha = lat + (long)prob * 2 * SM * T;
+    const float* beta = alpha + SM * T;
+    const float* A0 = alpha + (long)(2 * p) * T;
+    const float* A1 = p > 0 ? alpha + (long)(2 * p - 1) * T : nullptr;
+    const float* B1 = p < L ? beta + (long)(2 * p + 1) * T : nullptr;
+    const float* B2 = p < L ? beta + (long)(2 * p + 2) * T : nullptr;
+    const float* B3 = p < L - 1 ? beta + (long)(2 * p + 3) * T : nullptr;
+
+    auto load = [&](int t) {
+        EditFrame f;
+        t = min(t, len - 1);
+        const int tb = min(t + 1, len - 1);
+        f.lpc = lpb[t * tstride + cc];
+        f.lp0 = lpb[t * tstride];
+        f.a0 = A0[t];
+        f.a1 = A1 ? A1[t] : NEG_INF;
+        f.b1 = B1 ? B1[tb] : NEG_INF;
+        f.b2 = B2 ? B2[tb] : NEG_INF;
+        f.b3 = B3 ? B3[tb] : NEG_INF;
+        return f;
+    };
+
+    LseAcc acc_sub, acc_ins, acc_del;
+    if (p == 0 && L > 0) acc_del.add(lse2(B2[0], B3 ? B3[0] : NEG_INF));
+    const float e_last = p == L - 1 ? 0.f : NEG_INF;
+    float x = NEG_INF, y = NEG_INF, pa0 = NEG_INF, pa1 = NEG_INF;
+    EditFrame buf[PF];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) buf[k] = load(k);
+    for (int t0 = 0; t0 < len; t0 += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int t = t0 + k;
+            if (t < len) {                                       // uniform
+                const EditFrame f = buf[k];
+                buf[k] = load(t + PF);
+                const float xn = (t == 0 ? (p == 0 ? 0.f : NEG_INF) : lse3(x, pa0, skip_a ? pa1 : NEG_INF)) + f.lpc;
+                const float yn = t == 0 ? NEG_INF : lse2(y, x) + f.lp0;
+                const bool last = t == len - 1;
+                if (p < L) {
+                    const float e23 = last ? e_last : lse2(f.b2, f.b3);
+                    const float e2 = last ? e_last : f.b2;
+                    acc_sub.add(xn + (skip_b ? e23 : e2));
+                    if (!last) {
+                        if (ins_x) acc_ins.add(xn + f.b1);
+                        acc_ins.add(yn + f.b1);
+                    }
+                    if (p > 0) acc_del.add(f.a1 + (skip_d ? e23 : e2));
+                } else if (last) {
+                    acc_ins.add(xn);
+                    acc_ins.add(yn);
+                }
+                x = xn;
+                y = yn;
+                pa0 = f.a0;
+                pa1 = f.a1;
+            }
+        }
+    }
+    if (c < V) {
+        const bool valid = c > 0 && cls_c != 0;                  // the blank's class is no edit
+        ins[c] = valid ? acc_ins.get() : NEG_INF;
+        if (sub) sub[c] = (valid && p < L) ? acc_sub.get() : NEG_INF;
+    }
+    if (c == 0 && del) *del = p < L ? acc_del.get() : NEG_INF;
+}
+
+struct Plan {
+    int sp;                // extended positions rounded up to 64
+    size_t lds;            // dynamic LDS of the lattice kernel (0 when every labelling fits one wave)
+    size_t lattice_bytes;  // alpha and beta of every (line, hypothesis)
+    bool ok;
+};
+
+Plan plan_for(int t, int b, int v, int n, int max_label_len) {
+    Plan p = {0, 0, 0, false};
+    if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || n < 1 || n > NMAX || max_label_len < 0 || max_label_len > t) return p;
+    if ((long)t * b * n >= (1L << 31) || (long)b * n * (max_label_len + 1) >= (1L << 31)) return p;
+    p.sp = ((2 * max_label_len + 1 + 63) / 64) * 64;
+    p.lds = p.sp == 64 ? 0 : ((size_t)(p.sp + 2) + p.sp + (size_t)TB * p.sp) * 4;
+    p.lattice_bytes = (size_t)b * n * 2 * (2 * (size_t)max_label_len + 1) * t * sizeof(float);
+    p.ok = p.lds <= LDS_BUDGET && p.lattice_bytes <= LATTICE_BYTES_MAX;
+    return p;
+}
+
+size_t clp_bytes(int t, int b, int v) { return ((size_t)t * b * v * sizeof(float) + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" size_t vocr_ctc_edit_workspace_bytes(int t, int b, int v, int n, int max_label_len) {
+    const Plan p = plan_for(t, b, v, n, max_label_len);
+    if (!p.ok) return 0;
+    return clp_bytes(t, b, v) + p.lattice_bytes;
+}
+
+extern "C" int vocr_ctc_edit_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                    const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
+                                    float* out_ctc, float* out_sub, float* out_del, float* out_ins, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_ctc && out_sub && out_del && out_ins && workspace,
+                   "vocr_ctc_edit_scores: null pointer");
+    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "vocr_ctc_edit_scores: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", VMAX, t,
+                   b, v);
+    VOCR_CHECK_ARG(n >= 1 && n <= NMAX, "vocr_ctc_edit_scores: need 1 <= n <= %d (n=%d)", NMAX, n);
+    VOCR_CHECK_ARG(max_label_len >= 0 && max_label_len <= t && label_stride >= max_label_len,
+                   "vocr_ctc_edit_scores: need 0 <= max_label_len <= t and label_stride >= max_label_len (max_label_len=%d t=%d "
+                   "label_stride=%d)", max_label_len, t, label_stride);
+    const Plan p = plan_for(t, b, v, n, max_label_len);
+    VOCR_CHECK_ARG(p.ok, "vocr_ctc_edit_scores: unsupported shape (t=%d b=%d v=%d n=%d max_label_len=%d): the lattices of all labellings "
+                   "(%zu bytes) must fit %zu bytes and one row of the sweep (%zu bytes) the LDS", t, b, v, n, max_label_len,
+                   p.lattice_bytes, LATTICE_BYTES_MAX, p.lds);
+    const size_t need = vocr_ctc_edit_workspace_bytes(t, b, v, n, max_label_len);
+    VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_edit_scores: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    static bool lds_ok = false;
+    if (!lds_ok) {
+        const hipError_t e = hipFuncSetAttribute((const void*)ctc_edit_lattice_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)LDS_BUDGET);
+        if (e != hipSuccess) {
+            vocr_set_error("vocr_ctc_edit_scores: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+            return VOCR_ELAUNCH;
+        }
+        lds_ok = true;
+    }
+    float* clp = (float*)workspace;
+    float* lat = (float*)((char*)workspace + clp_bytes(t, b, v));
+    class_logprob_rows_kernel<<<vocr_cdiv((long)t * b, ROWS_PER_BLOCK), 256, 0, s>>>(logits, lens, canon, clp, t, b, v);
+    VOCR_CHECK_LAUNCH("vocr_ctc_edit_scores(class_logprob)");
+    ctc_edit_lattice_kernel<<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
+                                                          p.sp, lat, out_ctc);
+    VOCR_CHECK_LAUNCH("vocr_ctc_edit_scores(lattices)");
+    ctc_edit_scores_kernel<<<b * n * (max_label_len + 1), vocr_cdiv(v, 64) * 64, 0, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n,
+                                                                                        label_stride, max_label_len, lat, out_sub,
+                                                                                        out_del, out_ins);
+    VOCR_CHECK_LAUNCH("vocr_ctc_edit_scores(scores)");
+    return VOCR_OK;
+}

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .align import lines_from_arrays, one_copy
+from .align import alternatives_from_device, lines_from_arrays, one_copy
 from .textutils import uxxxx_to_utf8
 
 
@@ -86,6 +86,17 @@ class ArgmaxDecoder:
         labels, counts = labels.unsqueeze(1), counts.unsqueeze(1)
         return _aligned(model_output, lens_dev, labels, counts, None, canon, alphabet, uxxxx, 1)
 
+    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False, lang=None):
+        """(hypotheses as decode() returns them, per line a LineAlternatives of that hypothesis: CtcAligner.alternatives says what its
+        posteriors are).  The collapse's labels go to vocr_ctc_edit_scores on the device; one device-to-host copy at the end."""
+        alphabet = self.alphabet if lang is None else self.alphabet[lang]
+        dev = model_output.device
+        lens_dev = torch.as_tensor(_line_lengths(batch_actual_timesteps), dtype=torch.int32).to(dev)
+        idx, mx = ops.argmax_rows(model_output.detach())
+        canon = torch.as_tensor(alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        labels, counts = ops.greedy_collapse(idx, mx, lens_dev, canon, np.float32(3 * 1 / len(alphabet)))
+        return _alternatives(model_output, lens_dev, labels.unsqueeze(1), counts.unsqueeze(1), None, canon, alphabet, uxxxx, topk)
+
 
 class BeamDecoder:
     """CTC prefix beam search on the GPU (vocr_ctc_beam_search), optionally with a character n-gram LM (vistaocr_amd.lm.CharNgramLM):
@@ -126,6 +137,14 @@ class BeamDecoder:
         return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
                         self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
 
+    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False):
+        """(hypotheses as decode() returns them, per line a LineAlternatives of the best hypothesis, None where the search found none):
+        the search, then vocr_ctc_edit_scores on its device outputs, one device-to-host copy at the end.  The posteriors
+        (CtcAligner.alternatives says what they are) are those of the CTC model alone: the LM ranks the search, not the edits."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1)
+        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
+
     def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
         """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; labels are canonical alphabet indices,
         acoustic the CTC log-probability of the labelling, lm the LM log-probability including </s> (0 without an LM)."""
@@ -159,6 +178,15 @@ def _aligned(model_output, lens, labels, lengths, scores, canon, alphabet, uxxxx
         return hyps, [row[0] if np.isfinite(scores[b, 0, 0]) else None for b, row in enumerate(rows)]
     lists = _nbest_lists(labels, lengths, scores)
     return hyps, [[(h[0], h[1], row[q]) for q, h in enumerate(lst)] for lst, row in zip(lists, rows)]
+
+
+def _alternatives(model_output, lens, labels, lengths, scores, canon, alphabet, uxxxx, topk):
+    """decode_alternatives' common end for the device labellings [B,1,T] / [B,1] (scores [B,1,3] or None: every line has a hypothesis)."""
+    if scores is None:
+        scores = torch.zeros(labels.shape[0], 1, 3, dtype=torch.float32, device=labels.device)
+    rows, (labels, lengths, scores) = alternatives_from_device(model_output, lens, labels, lengths, canon, alphabet, topk, extra=[scores])
+    hyps = _best_strings(labels, lengths, scores, alphabet, uxxxx)
+    return hyps, [row[0] if np.isfinite(scores[b, 0, 0]) else None for b, row in enumerate(rows)]
 
 
 def _nbest_lists(labels, lengths, scores):
@@ -222,6 +250,14 @@ class WordBeamDecoder:
         labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest))
         return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
                         self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
+
+    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False):
+        """(hypotheses as decode() returns them, per line a LineAlternatives of the best hypothesis, None where the search found none):
+        the search, then vocr_ctc_edit_scores on its device outputs, one device-to-host copy at the end.  The posteriors
+        (CtcAligner.alternatives says what they are) are those of the CTC model alone: the LM ranks the search, not the edits."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1)
+        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
 
     def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
         """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; lm is the word LM's log-probability of the

@@ -246,7 +246,7 @@ def _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataload
     return hist
 
 
-def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None, aligner=None):
+def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None, aligner=None, alternatives=None):
     """The inference driver of src/decode_testset.py:42-206 without the LM branch: forward every batch, greedy-decode,
     and write `hyp-chars.txt` ("<uxxxx ...> (<utt-id>)") and `hyp-chars.txt.utf8` ("<utf8> (<utt-id minus last _part>)").
     The reference runs the decode in a background process because its per-frame numpy argmax is slow; here the argmax
@@ -258,7 +258,12 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     hypothesis is aligned to its frames and `hyp-words.tsv` is written as well, one row per token of form_tokenized_words:
     utt-id, token (uxxxx, characters joined by "_"), x0, x1 (input pixels, CtcAligner.pixel_spans: good to about one frame width),
     min_conf, mean_logp, tab-separated, in the decoder's (visual) order.  Without one (the default) exactly the two files above are
-    written.  Returns the number of lines written."""
+    written.  `alternatives`: None (the default: nothing changes) or k >= 1; with k, CtcAligner.alternatives (which says what its
+    posteriors are; `aligner`, or one made for the model's alphabet) is run on every hypothesis and `hyp-chars-alt.tsv` is written as
+    well, tab-separated: utt-id, position, uxxxx, posterior, then up to k `alt:posterior` pairs, best first (none that would print as 0.000000).  One row per character
+    (position p, its uxxxx, the posterior of keeping it; an alt of `<del>` means no character there) and one row per gap whose
+    posterior that nothing is missing is below 0.5 (position `^q` = before character q, `<gap>` in the uxxxx column, that posterior,
+    the most probable missing characters).  Returns the number of lines written."""
     import contextlib
     import os
     from .textutils import utf8_to_uxxxx, uxxxx_to_utf8
@@ -269,17 +274,33 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     model.eval()
     n = 0
     words_file = open(os.path.join(outdir, "hyp-words.tsv"), "w") if aligner is not None else contextlib.nullcontext()
+    alt_file = open(os.path.join(outdir, "hyp-chars-alt.tsv"), "w") if alternatives is not None else contextlib.nullcontext()
+    if alternatives is not None:
+        from .align import CtcAligner
+        alt_aligner = aligner if aligner is not None else CtcAligner(model.alphabet)
+
+    def pairs(alts):
+        return "".join("\t%s:%.6f" % ("<del>" if u is None else u, v) for u, v in alts if v >= 5e-7)      # not one that prints as 0
+
     with torch.no_grad(), open(os.path.join(outdir, "hyp-chars.txt"), "w") as fh, \
-            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw:
+            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw, alt_file as fha:
         for x, _target, widths, _target_lens, meta in dataloader:
             out, lens = model(x.cuda(non_blocking=True), widths)
-            if aligner is None:
+            if aligner is None and alternatives is None:
                 hyps = model.decode_without_lm(out, lens, uxxxx=False) if decoder is None else decoder.decode(out, lens, uxxxx=False)
             else:
                 # the same hypotheses in uxxxx form (decode's utf8 is uxxxx_to_utf8 of them), aligned as they stand
                 hyps_ux = model.decode_without_lm(out, lens, uxxxx=True) if decoder is None else decoder.decode(out, lens, uxxxx=True)
                 hyps = [uxxxx_to_utf8(h) for h in hyps_ux]
-                for i, al in enumerate(aligner.align(out, lens, hyps_ux)):
+                for i, la in enumerate(alt_aligner.alternatives(out, lens, hyps_ux, topk=alternatives) if alternatives is not None else ()):
+                    if la is None:
+                        continue
+                    for p, c in enumerate(la.chars):
+                        fha.write("%s\t%d\t%s\t%.6f%s\n" % (meta["utt-ids"][i], p, c.uxxxx, c.posterior, pairs(c.alternatives)))
+                    for q, (nothing, missing) in enumerate(la.gaps):
+                        if nothing < 0.5:
+                            fha.write("%s\t^%d\t<gap>\t%.6f%s\n" % (meta["utt-ids"][i], q, nothing, pairs(missing)))
+                for i, al in enumerate(aligner.align(out, lens, hyps_ux) if aligner is not None else ()):
                     if al is None:
                         continue
                     words = aligner.words(al)

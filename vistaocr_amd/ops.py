@@ -1345,12 +1345,9 @@ def ctc_word_beam_search(logits, lens, canon, lm, beam=16, nbest=1, lm_weight=0.
     return labels, out_lens, scores
 
 
-def ctc_align(logits, lens, labels, label_lens, canon=None):
-    """CTC forced alignment (vocr_ctc_align) of known labellings to raw logits [T,B,V].  `lens` as for ctc_beam_search; `labels` int32
-    device tensor [B,L] or [B,n,L] (the beam searches' out_labels goes in as it is), `label_lens` int32 device tensor [B] or [B,n];
-    `canon` int32 [V] device tensor of the symbol classes or None.  Returns, on the device and with the n axis only for 3-d labels,
-    (scores fp32 [B,n,2] = ln P(best path), ln P_ctc(labels | x); spans int32 [B,n,M,2] = first, last frame of each label, -1 where
-    there is none; label_scores fp32 [B,n,M,2] = peak, sum of the frame log-probability over the span), M = min(L, T) but at least 1."""
+def _labelling_args(what, workspace_fn, limits, logits, lens, labels, label_lens, canon):
+    """The argument checks and the 2-d / 3-d label convention ctc_align and ctc_edit_scores share.  Returns (logits, lens_dev, labels,
+    label_lens, n, stride, M, workspace bytes, squeeze)."""
     _need_gpu(logits, labels, label_lens)
     logits = _f32c(logits)
     T, B, V = logits.shape
@@ -1360,28 +1357,39 @@ def ctc_align(logits, lens, labels, label_lens, canon=None):
         labels, label_lens = labels.unsqueeze(1), label_lens.reshape(-1, 1)
     if labels.dim() != 3 or labels.shape[0] != B or labels.dtype != torch.int32 or label_lens.dtype != torch.int32 \
             or tuple(label_lens.shape) != tuple(labels.shape[:2]):
-        raise RuntimeError("ctc_align: labels must be int32 [B,L] or [B,n,L] and label_lens int32 [B] or [B,n] (labels %s, label_lens %s, "
-                           "B=%d)" % (tuple(labels.shape), tuple(label_lens.shape), B))
+        raise RuntimeError("%s: labels must be int32 [B,L] or [B,n,L] and label_lens int32 [B] or [B,n] (labels %s, label_lens %s, "
+                           "B=%d)" % (what, tuple(labels.shape), tuple(label_lens.shape), B))
     labels, label_lens = labels.contiguous(), label_lens.contiguous()
     n, stride = int(labels.shape[1]), int(labels.shape[2])
     if stride == 0:                                         # nothing to point at: one unused label per hypothesis
         labels, stride = torch.zeros(B, n, 1, dtype=torch.int32, device=dev), 1
     M = min(stride, T)
-    lib = _lib.load()
-    nbytes = lib.vocr_ctc_align_workspace_bytes(T, B, V, n, M)
+    nbytes = getattr(_lib.load(), workspace_fn)(T, B, V, n, M)
     if nbytes == 0:
-        raise RuntimeError("ctc_align: unsupported shape (T=%d B=%d V=%d n=%d label length %d; 2 <= V <= 256, n <= 128, T * B * n < "
-                           "2^31)" % (T, B, V, n, M))
+        raise RuntimeError("%s: unsupported shape (T=%d B=%d V=%d n=%d label length %d; %s)" % (what, T, B, V, n, M, limits))
     if torch.is_tensor(lens):
         lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
     else:
         lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
     if lens_dev.numel() != B:
-        raise RuntimeError("ctc_align: %d lengths for %d lines" % (lens_dev.numel(), B))
+        raise RuntimeError("%s: %d lengths for %d lines" % (what, lens_dev.numel(), B))
     if canon is not None:
         _need_gpu(canon)
         if canon.dtype != torch.int32 or canon.numel() != V:
-            raise RuntimeError("ctc_align: canon must be int32 [V]")
+            raise RuntimeError("%s: canon must be int32 [V]" % what)
+    return logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze
+
+
+def ctc_align(logits, lens, labels, label_lens, canon=None):
+    """CTC forced alignment (vocr_ctc_align) of known labellings to raw logits [T,B,V].  `lens` as for ctc_beam_search; `labels` int32
+    device tensor [B,L] or [B,n,L] (the beam searches' out_labels goes in as it is), `label_lens` int32 device tensor [B] or [B,n];
+    `canon` int32 [V] device tensor of the symbol classes or None.  Returns, on the device and with the n axis only for 3-d labels,
+    (scores fp32 [B,n,2] = ln P(best path), ln P_ctc(labels | x); spans int32 [B,n,M,2] = first, last frame of each label, -1 where
+    there is none; label_scores fp32 [B,n,M,2] = peak, sum of the frame log-probability over the span), M = min(L, T) but at least 1."""
+    logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze = _labelling_args(
+        "ctc_align", "vocr_ctc_align_workspace_bytes", "2 <= V <= 256, n <= 128, T * B * n < 2^31", logits, lens, labels, label_lens, canon)
+    T, B, V = logits.shape
+    dev = logits.device
     scores = torch.empty(B, n, 2, dtype=torch.float32, device=dev)
     spans = torch.empty(B, n, M, 2, dtype=torch.int32, device=dev)
     label_scores = torch.empty(B, n, M, 2, dtype=torch.float32, device=dev)
@@ -1391,3 +1399,28 @@ def ctc_align(logits, lens, labels, label_lens, canon=None):
     if squeeze:
         return scores[:, 0], spans[:, 0], label_scores[:, 0]
     return scores, spans, label_scores
+
+
+def ctc_edit_scores(logits, lens, labels, label_lens, canon=None):
+    """CTC edit scores (vocr_ctc_edit_scores): the exact forward score ln P_ctc of every labelling ONE edit away from each given
+    labelling.  Arguments as for ctc_align.  Returns, on the device, fp32, natural log, with the n axis only for 3-d labels and
+    M = min(L, T) but at least 1: (ctc [B,n] = ln P_ctc(labels | x); sub [B,n,M,V] = at [p][c] the score with label p replaced by the
+    class of column c (the label's own class: the unedited score; column 0 and the blank's class: -inf); del [B,n,M] = the score with
+    label p removed; ins [B,n,M+1,V] = at [q][c] the score with the class of column c inserted before label q, q = label length
+    appends).  Entries beyond a labelling's length are -inf."""
+    logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze = _labelling_args(
+        "ctc_edit_scores", "vocr_ctc_edit_workspace_bytes",
+        "2 <= V <= 256, n <= 128, label length <= 1823, B * n * 8 * T * (2 * label length + 1) bytes of lattices <= 2 GiB",
+        logits, lens, labels, label_lens, canon)
+    T, B, V = logits.shape
+    dev = logits.device
+    ctc = torch.empty(B, n, dtype=torch.float32, device=dev)
+    sub = torch.empty(B, n, M, V, dtype=torch.float32, device=dev)
+    dele = torch.empty(B, n, M, dtype=torch.float32, device=dev)
+    ins = torch.empty(B, n, M + 1, V, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    call("vocr_ctc_edit_scores", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(labels), _p(label_lens), n, stride, M, _p(ctc), _p(sub),
+         _p(dele), _p(ins), _p(ws), ws.numel() * 4, _stream())
+    if squeeze:
+        return ctc[:, 0], sub[:, 0], dele[:, 0], ins[:, 0]
+    return ctc, sub, dele, ins
