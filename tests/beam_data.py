@@ -1,5 +1,6 @@
 """Synthetic inputs of the beam-search tests: peaky logits (one dominant class per frame, mostly blank, at most one competitor per
-frame, every other class impossible) and a character 5-gram ARPA file written from random text.  Test helper only."""
+frame, every other class impossible), dense logits (every column finite, as an untrained model gives), dense logits with bitwise
+duplicated columns (exact score ties) and a character 5-gram ARPA file written from random text.  Test helper only."""
 import math
 from collections import Counter
 
@@ -25,6 +26,22 @@ def peaky_logits(rng, T, B, V, classes=None, p_char=0.35, p_alt=0.5, cost=(2.0, 
                     a = int(rng.choice(allc[allc != c]))
                     x[t, b, a] = x[t, b, c] - rng.uniform(*cost)
                 t += 1
+    return x
+
+
+def dense_logits(rng, T, B, V, sigma=3.0):
+    """[T, B, V] float32, every entry N(0, sigma): all K*V candidates of a frame are finite, so the selection cuts a large live set.
+    sigma = 3 keeps most lines decided (the restatement's smallest gap above the tests' TAU); sigma = 1 is too flat for that."""
+    return rng.normal(0.0, sigma, size=(T, B, V)).astype(np.float32)
+
+
+def tie_logits(rng, T, B, V, sigma, pairs):
+    """dense_logits with column dst a bitwise copy of column src for every (dst, src) of `pairs` (columns of different classes):
+    prefixes that differ only by swapping src and dst score exactly alike, in fp32 as in fp64, so cuts and final ranks fall inside
+    exact ties and the slot id decides them."""
+    x = dense_logits(rng, T, B, V, sigma)
+    for dst, src in pairs:
+        x[:, :, dst] = x[:, :, src]
     return x
 
 

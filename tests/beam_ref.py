@@ -6,7 +6,9 @@ stay / extend candidates, merging of an extension into the beam that already hol
 ranking by logsumexp(p_b, p_nb) + alpha * LM + beta * len under the total order (score desc, slot id k*V + c asc), optional pruning,
 and + alpha * ln P(</s>) before the final ranking (ties: the rank at the last frame).  It also returns the smallest score gap at
 any decision the search took (the K-th against the (K+1)-th candidate of every frame, and neighbouring ranks of the final n-best):
-where that gap is large, an fp32 search must take the same decisions."""
+where that gap is large, an fp32 search must take the same decisions.  It tracks the node ids the kernel assigns (a new prefix at
+frame t, rank q: t*K + q; a stay keeps its node) and can count, into a `stats` dict, the decisions that fell inside an exact tie,
+the merges into a prefix that came back under a new node id, and the largest number of finite candidates of a frame."""
 import itertools
 
 import numpy as np
@@ -55,9 +57,26 @@ def class_logprobs(logits, canon=None):
     return out
 
 
-def beam_search(logits, length, K, nbest=1, canon=None, lm=None, alpha=0.0, beta=0.0, prune=None):
+def tie_gap(values, v):
+    """The distance from the tied value v to the nearest different one of `values`, on either side (inf: there is none)."""
+    d = np.abs(values[values != v] - v)
+    return float(d.min()) if d.size else np.inf
+
+
+def beam_search(logits, length, K, nbest=1, canon=None, lm=None, alpha=0.0, beta=0.0, prune=None, exact_ties=False, stats=None):
     """One line: logits [T, V] raw.  lm: an object with logp [S,V], next [S,V], eos [S], start (CharNgramLM) or None.
-    Returns (hyps, min_gap): hyps = [(labels, total, acoustic, lm)] best first (at most nbest), min_gap the smallest decision gap."""
+    Returns (hyps, min_gap): hyps = [(labels, total, acoustic, lm)] best first (at most nbest), min_gap the smallest decision gap.
+
+    exact_ties: a gap of exactly 0.0 (the K-th against the (K+1)-th candidate, or neighbouring final ranks) does not enter min_gap;
+    the distance from the tied score to the nearest different candidate score on either side enters instead, and the total order
+    (score desc, slot id asc) decides the tie as the kernel does.  This is sound ONLY for logits whose tied candidates come from
+    bitwise-duplicated columns: such candidates go through identical operation sequences, so they are equal bit for bit in fp32 as
+    they are in fp64, and their slot ids descend from parents that are themselves the same beam or such twins.  On any other input
+    an fp64 tie says nothing about fp32, and the default (the tie counts as gap 0: the line is undecided) is the right one.
+
+    stats: a dict that receives, for this line, kth_ties (frames whose cut fell inside an exact tie), final_ties (exact ties between
+    neighbouring ranks of the final n-best), remerges (merges into a parent beam whose node id is not the one the child was created
+    from: the parent prefix left the beam and came back) and max_live (the largest number of finite candidates in a frame)."""
     logits = np.asarray(logits, dtype=np.float64)
     T, V = logits.shape
     L = int(min(max(length, 0), T))
@@ -72,6 +91,8 @@ def beam_search(logits, length, K, nbest=1, canon=None, lm=None, alpha=0.0, beta
     pb, pnb, acc = np.array([0.0]), np.array([NEG]), np.array([0.0])
     last, ln, lms = np.array([-1]), np.array([0]), np.array([start])
     pref = [()]
+    node, pnode = np.array([-1]), np.array([-1])            # the kernel's pool node of each beam, and that node's parent
+    kth_ties = final_ties = remerges = max_live = 0
     min_gap = np.inf
     cols = np.arange(V)
     for t in range(L):
@@ -90,6 +111,7 @@ def beam_search(logits, length, K, nbest=1, canon=None, lm=None, alpha=0.0, beta
             base = pb[k] if last[j] == last[k] else tot[k]
             spnb[j] = lse(spnb[j], base + xp[t, last[j]])
             merged.append((k, last[j]))
+            remerges += int(node[k] != pnode[j])
         base = np.where(cols[None, :] == last[:, None], pb[:, None], tot[:, None])
         ext = base + xp[t][None, :]
         score = ext + beta * (ln[:, None] + 1)
@@ -102,11 +124,19 @@ def beam_search(logits, length, K, nbest=1, canon=None, lm=None, alpha=0.0, beta
         flat = score.ravel()
         ids = np.nonzero(flat > NEG)[0]
         order = ids[np.lexsort((ids, -flat[ids]))]
+        max_live = max(max_live, len(order))
         if len(order) > K:
-            min_gap = min(min_gap, flat[order[K - 1]] - flat[order[K]])
+            gap = flat[order[K - 1]] - flat[order[K]]
+            if gap == 0.0:
+                kth_ties += 1
+                if exact_ties:
+                    gap = tie_gap(flat[ids], flat[order[K]])
+            min_gap = min(min_gap, gap)
         sel = order[:K]
         k, c = sel // V, sel % V
         st = c == 0
+        pnode = np.where(st, pnode[k], node[k])
+        node = np.where(st, node[k], t * K + np.arange(len(sel)))
         n_pb = np.where(st, spb[k], NEG)
         n_pnb = np.where(st, spnb[k], ext[k, c])
         if lm is not None:
@@ -123,7 +153,14 @@ def beam_search(logits, length, K, nbest=1, canon=None, lm=None, alpha=0.0, beta
     total = ac + (alpha * lmt if use_lm else 0.0) + beta * ln
     rank = np.lexsort((np.arange(len(total)), -total))
     for r in range(min(nbest, len(rank) - 1)):
-        min_gap = min(min_gap, total[rank[r]] - total[rank[r + 1]])
+        gap = total[rank[r]] - total[rank[r + 1]]
+        if gap == 0.0:
+            final_ties += 1
+            if exact_ties:
+                gap = tie_gap(total, total[rank[r]])
+        min_gap = min(min_gap, gap)
+    if stats is not None:
+        stats.update(kth_ties=kth_ties, final_ties=final_ties, remerges=remerges, max_live=max_live)
     hyps = [(list(pref[i]), float(total[i]), float(ac[i]), float(lmt[i])) for i in rank[:nbest]]
     return hyps, min_gap
 

@@ -1,11 +1,13 @@
 """CPU: the character n-gram LM's resolved tables (vistaocr_amd/lm.py) against a direct ARPA backoff lookup, the fp64 restatement of
-the beam search (tests/beam_ref.py) against brute force, and the argument validation of the beam-search entry points (no launch)."""
+the beam search (tests/beam_ref.py) against brute force, its exact-tie rule and counters on the pinned inputs of the fp64 seam tests
+(tests/beam_cases.py), and the argument validation of the beam-search entry points (no launch)."""
 import ctypes
 import math
 
 import numpy as np
 import pytest
 
+from tests import beam_cases as bc
 from tests import beam_ref as br
 from vistaocr_amd.alphabet import Alphabet
 from vistaocr_amd.lm import CharNgramLM
@@ -235,6 +237,93 @@ def test_restatement_equals_brute_force(tmp_path, with_lm, T, ncls, K):
         assert lab == blab
         assert abs(tot - btot) < 1e-9 * max(1.0, abs(btot)) and abs(ac - bac) < 1e-9 * max(1.0, abs(bac))
         assert abs(lmv - blm) < 1e-9 * max(1.0, abs(blm))
+
+
+@pytest.mark.parametrize("with_lm", [False, True])
+@pytest.mark.parametrize("T,ncls,K", [(5, 2, 64), (4, 3, 128)])
+def test_restatement_with_exact_ties_equals_brute_force(tmp_path, with_lm, T, ncls, K):
+    """The brute-force agreement holds with exact_ties=True: hypotheses and scores are the default's, nothing is pruned so no prefix
+    ever comes back (remerges = 0), and every finite candidate of the fullest frame is counted."""
+    lm = _tiny_lm(tmp_path) if with_lm else None
+    alpha, beta = (0.7, 0.3) if with_lm else (0.0, 0.2)
+    rng = np.random.default_rng(T * 10 + ncls)
+    logits = rng.normal(0, 1.5, size=(T, len(ALPHA)))
+    logits[:, ncls + 1:] = -np.inf
+    brute = br.brute_force(logits, list(range(1, ncls + 1)), lm=lm, alpha=alpha, beta=beta)
+    stats = {}
+    hyps, gap = br.beam_search(logits, T, K, nbest=len(brute), lm=lm, alpha=alpha, beta=beta, exact_ties=True, stats=stats)
+    assert hyps == br.beam_search(logits, T, K, nbest=len(brute), lm=lm, alpha=alpha, beta=beta)[0]
+    assert [h[0] for h in hyps] == [h[0] for h in brute]
+    for h, b in zip(hyps, brute):
+        assert np.allclose(h[1:], b[1:], rtol=1e-9, atol=1e-9)
+    assert stats["remerges"] == 0 and stats["kth_ties"] == 0 and stats["final_ties"] == 0
+    assert 0 < stats["max_live"] <= sum(ncls ** n for n in range(T)) * (ncls + 1)        # the prefixes before the last frame
+
+
+def test_exact_ties_rule():
+    """Two bitwise-equal columns: the default sees gap 0.0 (the line is undecided); with exact_ties the tie is decided by the slot id
+    and what enters min_gap is the distance to the nearest different score, which tie_gap finds on either side."""
+    assert br.tie_gap(np.array([3.0, 1.0, 1.0, 0.5, -np.inf]), 1.0) == 0.5
+    assert br.tie_gap(np.array([1.25, 1.0, 1.0, 0.5]), 1.0) == 0.25
+    assert br.tie_gap(np.array([1.0, 1.0]), 1.0) == np.inf
+    x = np.array([[0.0, 1.0, 1.0, -1.0]] * 2)                        # classes 1 and 2 tie in every frame
+    s0, s1 = {}, {}
+    h0, g0 = br.beam_search(x, 2, 2, nbest=2, stats=s0)
+    h1, g1 = br.beam_search(x, 2, 2, nbest=2, exact_ties=True, stats=s1)
+    assert g0 == 0.0 and g1 > 0.1 and h0 == h1 and s0 == s1
+    # frame 1 has 2 stays and 4 finite extensions (a repeat needs a blank first: the other 2 are -inf)
+    assert s0["final_ties"] == 1 and s0["kth_ties"] == 0 and s0["max_live"] == 6
+    assert [h[0] for h in h1] == [[1], [2]]                          # the smaller slot id first
+    h2, g2 = br.beam_search(x, 2, 1, nbest=1, exact_ties=True, stats=s1)
+    assert s1["kth_ties"] == 1 and h2[0][0] == [1] and g2 > 0.1       # K = 1: frame 0 cuts between the twins
+
+
+ALL_CHAR = bc.CHAR_DENSE + bc.CHAR_VARIANTS + ["big_K128_V256"] + bc.CHAR_INTERMEDIATE + bc.CHAR_TIES + bc.CHAR_COMEBACK
+
+
+def test_every_pinned_case_is_listed():
+    assert sorted(ALL_CHAR) == sorted(bc.CHAR_CASES)
+
+
+@pytest.mark.parametrize("name", ALL_CHAR)
+def test_pinned_inputs_meet_floors_and_counters(name):
+    """The inputs of tests/test_beam_fp64_gpu.py, by the restatement alone: at least half of the lines of every case are decided by
+    TAU; the dense cases have K*V/2 live candidates on every compared line; the tie cases cut inside exact ties and rank exact ties;
+    every come-back line merges into a prefix that returned under a new node id."""
+    case, ref = bc.char_case(name), bc.char_reference(name)
+    bc.check_pinned(name, case, ref)
+    if name in bc.CHAR_TIES:
+        assert case.exact_ties and bc.total(case, ref, "kth_ties") > 0 and bc.total(case, ref, "final_ties") > 0
+        for dst, src in (bc.ENGLISH_PAIRS if name == "tie_english_K16" else bc.V12_PAIRS):
+            assert case.x[:, :, dst].tobytes() == case.x[:, :, src].tobytes()
+    else:
+        assert not case.exact_ties
+    if name in bc.CHAR_COMEBACK:
+        assert all(r.stats["remerges"] > 0 and r.gap >= bc.TAU for r in ref)
+    if name == "ragged_K16_lm":
+        T = case.x.shape[0]
+        assert {0, 1, T} <= set(case.lens) and max(case.lens) > T
+        assert all(ref[b].stats["max_live"] >= case.K * case.x.shape[2] / 2 for b in bc.decided(case, ref) if case.lens[b] >= 3)
+    if name in bc.CHAR_INTERMEDIATE:
+        assert case.lens == list(range(1, case.x.shape[0] + 1)) and case.nbest == case.K
+
+
+def test_hand_built_come_back():
+    """HAND_PROBS: "a" is cut after frame 1 while "" and its child "ab" stay, comes back from "" at frame 2 under a new node id,
+    and the merge of a + b into ab at frame 3 crosses the two ids.  The beams after frames 0 - 2 are the ones written down in
+    HAND_KEPT, and the final beam is the brute force over the alignments those beams can still see."""
+    x = bc.hand_logits()[:, 0]
+    K = bc.HAND_K
+    for t, kept in enumerate(bc.HAND_KEPT):
+        hyps, _ = br.beam_search(x, t + 1, K, nbest=K)
+        assert {tuple(h[0]) for h in hyps} == kept, t
+    stats = {}
+    hyps, gap = br.beam_search(x, 4, K, nbest=K, stats=stats)
+    assert stats["remerges"] == 1 and gap > 1e-2
+    want = sorted(bc.kept_path_scores(br.class_logprobs(x), bc.HAND_KEPT).items(), key=lambda kv: -kv[1])[:K]
+    assert [tuple(h[0]) for h in hyps] == [w[0] for w in want]
+    assert np.allclose([h[2] for h in hyps], [w[1] for w in want], rtol=0, atol=1e-12)
+    assert (1, 2) in [w[0] for w in want]
 
 
 def test_restatement_merges_repeats_and_classes():

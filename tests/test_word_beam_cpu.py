@@ -1,11 +1,13 @@
 """CPU: the word n-gram LM's tables (vistaocr_amd/lm.py WordNgramLM) against a direct ARPA backoff lookup, its lexicon trie and
-look-ahead, the fp64 restatement of the word beam search (tests/word_beam_ref.py) against brute force, and the argument validation
-of the word beam-search entry points (no launch)."""
+look-ahead, the fp64 restatement of the word beam search (tests/word_beam_ref.py) against brute force, its exact-tie rule and counters
+on the pinned inputs of the fp64 seam tests (tests/beam_cases.py), and the argument validation of the word beam-search entry points
+(no launch)."""
 import ctypes
 
 import numpy as np
 import pytest
 
+from tests import beam_cases as bc
 from tests import word_beam_ref as wr
 from vistaocr_amd.alphabet import Alphabet
 from vistaocr_amd.lm import KIND_LETTER, KIND_SINGLE, KIND_SPACE, LN10, WordNgramLM, _parse_arpa
@@ -174,6 +176,54 @@ def test_restatement_equals_brute_force(tmp_path, T, cls, alpha, beta, oov):
         assert lab == blab
         assert abs(tot - btot) < 1e-9 * max(1.0, abs(btot)) and abs(ac - bac) < 1e-9 * max(1.0, abs(bac))
         assert abs(lmv - blm) < 1e-9 * max(1.0, abs(blm))
+
+
+@pytest.mark.parametrize("oov", [None, -2.5])
+@pytest.mark.parametrize("T,cls", CASES)
+def test_restatement_with_exact_ties_equals_brute_force(tmp_path, T, cls, oov):
+    """The brute-force agreement holds with exact_ties=True: the hypotheses are the default's and the brute force's, and with every
+    prefix held no prefix ever comes back."""
+    lm, grams = _lm(tmp_path, ARPA3)
+    rng = np.random.default_rng(T * 100 + sum(cls))
+    logits = rng.normal(0, 1.5, size=(T, len(ALPHA)))
+    mask = np.ones(len(ALPHA), dtype=bool)
+    mask[[0] + cls] = False
+    logits[:, mask] = -np.inf
+    brute = wr.brute_force(logits, cls, ALPHA, grams, alpha=0.9, beta=0.4, oov=oov)
+    stats = {}
+    hyps, _ = wr.beam_search(logits, T, 128, lm, nbest=len(brute), alpha=0.9, beta=0.4, oov=oov, exact_ties=True, stats=stats)
+    assert hyps == wr.beam_search(logits, T, 128, lm, nbest=len(brute), alpha=0.9, beta=0.4, oov=oov)[0]
+    assert [h[0] for h in hyps] == [b[0] for b in brute]
+    for h, b in zip(hyps, brute):
+        assert np.allclose(h[1:], b[1:], rtol=1e-9, atol=1e-9)
+    assert stats["remerges"] == 0 and stats["kth_ties"] == 0 and stats["max_live"] > 0
+
+
+ALL_WORD = bc.WORD_DENSE + ["w_big_K128_V256", "w_tie_lm_K6"]
+
+
+def test_every_pinned_case_is_listed():
+    assert sorted(ALL_WORD) == sorted(bc.WORD_CASES)
+
+
+@pytest.mark.parametrize("name", ALL_WORD)
+def test_pinned_inputs_meet_floors_and_counters(name):
+    """The inputs of tests/test_word_beam_fp64_gpu.py, by the restatement alone: at least half of the lines of every case are decided
+    by TAU, the open-vocabulary dense cases have K*V/2 live candidates on every compared line, some closed-vocabulary lines output
+    nothing, and the LM tie case (letters d and e start no lexicon word and share one column bit for bit, so both enter the OOV
+    state with the same look-ahead and close score) cuts inside exact ties and ranks exact ties."""
+    case, ref = bc.word_case(name), bc.word_reference(name)
+    bc.check_pinned(name, case, ref)
+    if name == "w_tie_lm_K6":
+        assert case.exact_ties and case.alpha != 0 and case.oov is not None
+        assert bc.total(case, ref, "kth_ties") > 0 and bc.total(case, ref, "final_ties") > 0
+        assert case.x[:, :, 8].tobytes() == case.x[:, :, 7].tobytes()
+        assert all(case.lm.trie_next[0, c] <= 0 and case.lm.kind[c] == KIND_LETTER for c in (7, 8))
+    else:
+        assert not case.exact_ties
+    if name in ("w_K5_closed", "w_K16_closed"):
+        lines = bc.decided(case, ref)
+        assert 0 < sum(1 for b in lines if not ref[b].hyps) < len(lines)
 
 
 def test_restatement_closed_vocabulary_drops_open_words(tmp_path):

@@ -6,7 +6,8 @@ order (score desc, slot id k*V + c asc), the end-of-line ranking with ties by th
 inside an open word at a trie node or OOV; it is ranked by logsumexp(p_b, p_nb) + alpha * (LM of its closed tokens + look-ahead) +
 beta * closed tokens; letters step the trie, spaces close the open word, singles close it and add their token; candidates whose LM
 term is -inf are never taken; at the end the open word is closed and </s> added, and beams whose word cannot close are dropped.  It
-reads the resolved tables of WordNgramLM.  It also returns the smallest score gap at any decision the search took.
+reads the resolved tables of WordNgramLM.  It also returns the smallest score gap at any decision the search took, and takes
+beam_ref.beam_search's `exact_ties` and `stats` keywords with the same meaning (node ids tracked as the kernel assigns them).
 
 The brute force shares nothing with those tables: every labelling is scored by beam_ref.ctc_logprob, textutils.form_tokenized_words
 and a direct recursive ARPA backoff over the parsed n-gram dict."""
@@ -76,9 +77,13 @@ class _Tables(object):
         return (OUT, acc, lms, ntok, 0.0, 0.0, lms)
 
 
-def beam_search(logits, length, K, lm, nbest=1, canon=None, alpha=0.0, beta=0.0, oov=None):
+def beam_search(logits, length, K, lm, nbest=1, canon=None, alpha=0.0, beta=0.0, oov=None, exact_ties=False, stats=None):
     """One line: logits [T, V] raw, lm a WordNgramLM, oov the oov_penalty (None: closed vocabulary).  Returns (hyps, min_gap):
-    hyps = [(labels, total, acoustic, lm)] best first (at most nbest), min_gap the smallest decision gap."""
+    hyps = [(labels, total, acoustic, lm)] best first (at most nbest), min_gap the smallest decision gap.
+
+    exact_ties, stats: as in beam_ref.beam_search.  exact_ties is sound ONLY where the tied candidates come from bitwise-duplicated
+    columns whose classes the LM also treats alike (the same kind, trie step, look-ahead and close score), so that they go through
+    identical operation sequences in fp32 and in fp64."""
     logits = np.asarray(logits, dtype=np.float64)
     T, V = logits.shape
     L = int(min(max(length, 0), T))
@@ -92,6 +97,8 @@ def beam_search(logits, length, K, lm, nbest=1, canon=None, alpha=0.0, beta=0.0,
     last, ln = np.array([-1]), np.array([0])
     state = [(OUT, 0.0, lm.start, 0, 0.0, 0.0, lm.start)]
     pref = [()]
+    node, pnode = [-1], [-1]                                # the kernel's pool node of each beam, and that node's parent
+    kth_ties = final_ties = remerges = max_live = 0
     min_gap = np.inf
     for t in range(L):
         nb = len(pref)
@@ -109,6 +116,7 @@ def beam_search(logits, length, K, lm, nbest=1, canon=None, alpha=0.0, beta=0.0,
             base = pb[k] if last[j] == last[k] else tot[k]
             spnb[j] = br.lse(spnb[j], base + xp[t, last[j]])
             merged.append((k, last[j]))
+            remerges += int(node[k] != pnode[j])
         score = np.full((nb, V), NEG)
         ext_state = {}
         cols = [c for c in range(1, V) if xp[t, c] > NEG]
@@ -127,22 +135,28 @@ def beam_search(logits, length, K, lm, nbest=1, canon=None, alpha=0.0, beta=0.0,
         flat = score.ravel()
         ids = np.nonzero(flat > NEG)[0]
         order = ids[np.lexsort((ids, -flat[ids]))]
+        max_live = max(max_live, len(order))
         if len(order) > K:
-            min_gap = min(min_gap, flat[order[K - 1]] - flat[order[K]])
+            gap = flat[order[K - 1]] - flat[order[K]]
+            if gap == 0.0:
+                kth_ties += 1
+                if exact_ties:
+                    gap = br.tie_gap(flat[ids], flat[order[K]])
+            min_gap = min(min_gap, gap)
         sel = order[:K]
-        n_pb, n_pnb, n_last, n_ln, n_state, n_pref = [], [], [], [], [], []
-        for i in sel:
+        n_pb, n_pnb, n_last, n_ln, n_state, n_pref, n_node, n_pnode = [], [], [], [], [], [], [], []
+        for q, i in enumerate(sel):
             k, c = int(i) // V, int(i) % V
             if c == 0:
                 n_pb.append(spb[k]); n_pnb.append(spnb[k]); n_last.append(last[k]); n_ln.append(ln[k])
-                n_state.append(state[k]); n_pref.append(pref[k])
+                n_state.append(state[k]); n_pref.append(pref[k]); n_node.append(node[k]); n_pnode.append(pnode[k])
             else:
                 base = pb[k] if c == last[k] else tot[k]
                 n_pb.append(NEG); n_pnb.append(base + xp[t, c]); n_last.append(c); n_ln.append(ln[k] + 1)
-                n_state.append(ext_state[(k, c)]); n_pref.append(pref[k] + (c,))
+                n_state.append(ext_state[(k, c)]); n_pref.append(pref[k] + (c,)); n_node.append(t * K + q); n_pnode.append(node[k])
         pb, pnb = np.array(n_pb, dtype=np.float64), np.array(n_pnb, dtype=np.float64)
         last, ln = np.array(n_last, dtype=np.int64), np.array(n_ln, dtype=np.int64)
-        state, pref = n_state, n_pref
+        state, pref, node, pnode = n_state, n_pref, n_node, n_pnode
     ac = br.lse(pb, pnb)
     total, lmt = np.full(len(pref), NEG), np.full(len(pref), NEG)
     for j, (wn, acc, lms, ntok, la, clp, cst) in enumerate(state):
@@ -155,7 +169,14 @@ def beam_search(logits, length, K, lm, nbest=1, canon=None, alpha=0.0, beta=0.0,
     rank = np.lexsort((np.arange(len(total)), -total))
     rank = [r for r in rank if total[r] > NEG]
     for r in range(min(nbest, len(rank) - 1)):
-        min_gap = min(min_gap, total[rank[r]] - total[rank[r + 1]])
+        gap = total[rank[r]] - total[rank[r + 1]]
+        if gap == 0.0:
+            final_ties += 1
+            if exact_ties:
+                gap = br.tie_gap(total[total > NEG], total[rank[r]])
+        min_gap = min(min_gap, gap)
+    if stats is not None:
+        stats.update(kth_ties=kth_ties, final_ties=final_ties, remerges=remerges, max_live=max_live)
     hyps = [(list(pref[i]), float(total[i]), float(ac[i]), float(lmt[i])) for i in rank[:nbest]]
     return hyps, min_gap
 
