@@ -512,6 +512,41 @@ int vocr_ctc_edit_scores(const float* logits, const int32_t* lens, int t, int b,
                          float* out_ctc, float* out_sub, float* out_del, float* out_ins,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC keyword search: "does this line contain the word X" without decoding (the lattice use of eesen's decode, lattice-free) ---- */
+/* For every (line b, query q) the EXPECTED NUMBER of occurrences of the query as a contiguous substring of the collapsed labelling,
+ * E = sum over all frame paths pi of P(pi | x) * #occurrences(query in B(pi)): exact under the CTC model, a sum over all v^len paths
+ * with no beam, no hypothesis and no pruning; min(1, E) bounds the probability that the query occurs at all from above (E is NOT that
+ * probability, and no language model is involved).  And the best single occurrence with its frame span.  Inputs, classes, blank and
+ * transition rule are vocr_ctc_align's; "equal" and "different" always compare classes.  queries[nq][query_stride], query_lens[nq],
+ * query_flags[nq] (NULL: all 0) device int32, shared by all lines.  A query k_1 .. k_L (no blanks) has S = 2L-1 extended positions
+ * k_1, blank, k_2, .., blank, k_L.  An occurrence is a MAXIMAL frame span [s, e]: pi_s in k_1's class, pi_e in k_L's, pi_s .. pi_e
+ * collapses to the query, pi_(s-1) not in k_1's class (or s = 0), pi_(e+1) not in k_L's class (or e = len-1).  One pass, with
+ * notc_t(c) = ln(1 - P_t(class of c)) computed as the log of the SUM over the other classes' columns (never 1 - p):
+ *   entry(t) = 0 if t = 0 else notc_(t-1)(k_1);  exit(t) = 0 if t = len-1 else notc_(t+1)(k_L);
+ *   a_t(0) = lp_t(k_1) + lse(a_(t-1)(0), entry(t));  a_t(s) = lp_t(ext_s) + lse(a_(t-1)(s), a_(t-1)(s-1), a_(t-1)(s-2) if the skip is
+ *   allowed);  ln E = lse over t of a_t(S-1) + exit(t).
+ * query_flags bit 0 (ANCHOR_START): only occurrences at the very beginning of the labelling, entry(t) = sum of ln p_u(blank), u < t;
+ * bit 1 (ANCHOR_END): the same at the end, exit(t) = sum of ln p_u(blank), u > t; both bits: E = P_ctc(query | x), vocr_ctc_align's
+ * second score.  Bits 2 / 3 (TRIM_START / TRIM_END) change only the reported span: it starts at the first frame of k_2 / ends at the
+ * last frame of k_(L-1) (a whole-word search pads the word with spaces and wants the word's frames); such a query needs L >= 2, with
+ * both bits L >= 3.  The best occurrence is the same recursion with max: the maximum over spans and over the paths inside them of
+ * entry(s) + sum of lp_t(pi_t) + exit(e); every cell carries the start frame of its best path (no back-pointer table).  Tie rule:
+ * among equal candidates prefer s (stay), then s-1, then s-2, then the fresh entry (position 0 only); among equal end frames the
+ * earliest wins.  Outputs: out_log_count[B][nq] = ln E (-inf for 0); out_best[B][nq] = the best occurrence's score;
+ * out_span[B][nq][2] = its {first, last} frame (inclusive).  -inf / -inf / {-1, -1}: a query that does not fit the line's frames or
+ * uses a class the frames give -inf, lens[b] = 0, and for every line an invalid query (query_lens outside [1, max_query_len], a label
+ * <= 0 or >= v or in the blank's class, too few labels for its trim bits); an invalid query poisons only its own column.  -inf logits are legal and never yield NaN (a
+ * frame whose logits are all -inf gives -inf to every class and every notc).  Results are bit-identical from run to run, and written
+ * at the caller's query index: the queries are sorted by length on the device so that those of at most 8 / 16 labels share a wave,
+ * 4 / 2 per wave.  Limits: 2 <= v <= 256, nq >= 1, 1 <= max_query_len <= 128, query_stride >= max_query_len, t * b * nq < 2^31.
+ * Workspace (class log-probabilities, notc rows, blank prefix / suffix sums, the sort) from vocr_ctc_keyword_workspace_bytes (0 for an
+ * unsupported shape); an unsupported shape fails with VOCR_EINVAL before any launch. */
+size_t vocr_ctc_keyword_workspace_bytes(int t, int b, int v, int nq, int max_query_len);
+int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                            const int32_t* queries, const int32_t* query_lens, const int32_t* query_flags, int nq, int query_stride,
+                            int max_query_len, float* out_log_count, float* out_best, int32_t* out_span,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

@@ -1,0 +1,102 @@
+"""CTC keyword search on the GPU (vocr_ctc_keyword_scores): does this line contain the word X, asked of the network's output itself
+instead of a decoded 1-best.
+
+WHAT THE NUMBER IS: for a line and a keyword, the EXPECTED NUMBER of times the keyword occurs as a contiguous run of characters in the
+line's labelling, the expectation taken over ALL frame paths under the CTC model (exact: no beam, no hypothesis, no pruning).
+min(1, expected count) bounds the probability that the keyword occurs at all from above.  It is NOT that probability (two overlapping
+or repeated occurrences on one path count twice), no language model is involved, and characters are compared as the alphabet's symbol
+strings (indices with the same string are one character, as everywhere in this package)."""
+import re
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .align import one_copy
+from .textutils import utf8_to_uxxxx
+
+KeywordHits = namedtuple("KeywordHits", "keywords log_count expected_count prob_upper best_logp best_span")
+
+ANCHOR_START, ANCHOR_END, TRIM_START, TRIM_END = 1, 2, 4, 8
+_UXXXX = re.compile(r"^u[0-9a-f]{4,6}$")
+
+
+class KeywordSpotter:
+    """Searches the model's output frames for keywords.  whole_word=True counts only occurrences bounded on both sides by a space
+    (u0020) or by the line's ends."""
+
+    def __init__(self, alphabet, whole_word=False):
+        self.alphabet = alphabet
+        self.whole_word = bool(whole_word)
+        self._canon = {}
+        if self.whole_word and "u0020" not in alphabet.char_to_idx:
+            raise ValueError("KeywordSpotter(whole_word=True): the alphabet has no u0020 (space), so words have no boundaries to search for")
+        self._space = alphabet.char_to_idx.get("u0020")
+
+    def canon(self, dev):
+        key = str(dev)
+        if key not in self._canon:
+            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        return self._canon[key]
+
+    def labels(self, keyword):
+        """A keyword as alphabet indices: a utf-8 string ("the"), a string of space-joined uxxxx tokens ("u0074 u0068 u0065": taken as
+        such when every token is one of the alphabet's), or a sequence of indices.  A string is read by that rule alone, so the literal
+        text "u0061" cannot be searched for as a string where u0061 is in the alphabet: pass such a keyword as indices, the one form
+        that is never interpreted."""
+        if not isinstance(keyword, str):
+            return [int(v) for v in keyword]
+        toks = keyword.split()
+        if not (toks and all(_UXXXX.match(t) and t in self.alphabet.char_to_idx for t in toks)):
+            toks = utf8_to_uxxxx(keyword, output_array=True)
+        missing = [t for t in toks if t not in self.alphabet.char_to_idx]
+        if missing or not toks:
+            raise ValueError("keyword %r: %s" % (keyword, "empty" if not toks else "not in the alphabet: " + " ".join(missing)))
+        return [self.alphabet.char_to_idx[t] for t in toks]
+
+    def _queries(self, keywords):
+        """(int32 [Q', L] labels, [Q'] lengths, [Q'] flags, queries per keyword)."""
+        labs = [self.labels(k) for k in keywords]
+        if self.whole_word:
+            sp = self._space
+            qs, flags = [], []
+            for l in labs:                    # sp q sp | ^q sp | sp q$ | ^q$: disjoint, and every whole-word occurrence is one of them
+                qs += [[sp] + l + [sp], l + [sp], [sp] + l, l]
+                flags += [TRIM_START | TRIM_END, ANCHOR_START | TRIM_END, ANCHOR_END | TRIM_START, ANCHOR_START | ANCHOR_END]
+            per = 4
+        else:
+            qs, flags, per = labs, [0] * len(labs), 1
+        L = max([len(q) for q in qs] + [1])
+        lab = np.zeros((len(qs), L), dtype=np.int32)
+        for i, q in enumerate(qs):
+            lab[i, :len(q)] = q
+        return lab, np.array([len(q) for q in qs], dtype=np.int32), np.array(flags, dtype=np.int32), per
+
+    def search(self, model_output, lens, keywords):
+        """`model_output` [T,B,V] logits on the device, `lens` the lines' frame counts, `keywords` a list (forms: labels()).  Returns
+        KeywordHits of host arrays: log_count [B,Q] (natural log of the expected count, -inf for 0), expected_count, prob_upper =
+        min(1, expected count), best_logp [B,Q] (the score of the best single occurrence: its frames' log-probabilities and the two
+        boundary terms) and best_span [B,Q,2] (its first and last frame, inclusive; -1 where there is none).  One device-to-host copy.
+        With whole_word the count is the sum over the four ways a word can be bounded (space or line end on either side), the best
+        occurrence is the best of the four, and its span holds the word's frames without the bounding spaces'."""
+        keywords = list(keywords)
+        B = int(model_output.shape[1])
+        if not keywords:
+            z = np.zeros((B, 0), dtype=np.float32)
+            return KeywordHits([], z, z, z, z, np.zeros((B, 0, 2), dtype=np.int32))
+        lab, ln, flags, per = self._queries(keywords)
+        dev = model_output.device
+        lc, best, span = ops.ctc_keyword_scores(model_output.detach(), lens, torch.from_numpy(lab).to(dev), torch.from_numpy(ln).to(dev),
+                                                torch.from_numpy(flags).to(dev), self.canon(dev))
+        Q = len(keywords)
+        if per > 1:                                                           # on the device: the sum of the four and the best of them
+            lc, best, span = lc.view(B, Q, per), best.view(B, Q, per), span.view(B, Q, per, 2)
+            lc = torch.logsumexp(lc.double(), dim=2).float()
+            best, which = best.max(dim=2)
+            span = span.gather(2, which.view(B, Q, 1, 1).expand(B, Q, 1, 2)).squeeze(2)
+        lc, best, span = one_copy([lc.unsqueeze(-1), best.unsqueeze(-1), span])
+        lc, best = lc[..., 0], best[..., 0]
+        with np.errstate(over="ignore"):
+            count = np.exp(lc.astype(np.float64))
+        return KeywordHits(keywords, lc, count, np.minimum(1.0, count), best, span)

@@ -246,7 +246,8 @@ def _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataload
     return hist
 
 
-def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None, aligner=None, alternatives=None):
+def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None, aligner=None, alternatives=None,
+                   spotter=None, keywords=None, min_count=0.5):
     """The inference driver of src/decode_testset.py:42-206 without the LM branch: forward every batch, greedy-decode,
     and write `hyp-chars.txt` ("<uxxxx ...> (<utt-id>)") and `hyp-chars.txt.utf8` ("<utf8> (<utt-id minus last _part>)").
     The reference runs the decode in a background process because its per-frame numpy argmax is slow; here the argmax
@@ -263,7 +264,11 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     well, tab-separated: utt-id, position, uxxxx, posterior, then up to k `alt:posterior` pairs, best first (none that would print as 0.000000).  One row per character
     (position p, its uxxxx, the posterior of keeping it; an alt of `<del>` means no character there) and one row per gap whose
     posterior that nothing is missing is below 0.5 (position `^q` = before character q, `<gap>` in the uxxxx column, that posterior,
-    the most probable missing characters).  Returns the number of lines written."""
+    the most probable missing characters).  `spotter` (a vistaocr_amd.KeywordSpotter, which says what its numbers are) and `keywords`
+    (a list in the forms KeywordSpotter.search takes): with both, every line is searched for every keyword and `hyp-kws.tsv` is written
+    as well, tab-separated: utt-id, keyword (as given; an index list joined by spaces), expected_count, best_logp, x0, x1 (input pixels
+    of the best occurrence, CtcAligner.pixel_spans' geometry), one row for every (line, keyword) that has an occurrence at all and
+    whose expected count is at least `min_count`.  Without them (the default) nothing changes.  Returns the number of lines written."""
     import contextlib
     import os
     from .textutils import utf8_to_uxxxx, uxxxx_to_utf8
@@ -275,6 +280,8 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     n = 0
     words_file = open(os.path.join(outdir, "hyp-words.tsv"), "w") if aligner is not None else contextlib.nullcontext()
     alt_file = open(os.path.join(outdir, "hyp-chars-alt.tsv"), "w") if alternatives is not None else contextlib.nullcontext()
+    kws_file = open(os.path.join(outdir, "hyp-kws.tsv"), "w") if spotter is not None and keywords is not None else contextlib.nullcontext()
+    kws_names = [k if isinstance(k, str) else " ".join(str(int(v)) for v in k) for k in keywords] if keywords is not None else []
     if alternatives is not None:
         from .align import CtcAligner
         alt_aligner = aligner if aligner is not None else CtcAligner(model.alphabet)
@@ -283,7 +290,7 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
         return "".join("\t%s:%.6f" % ("<del>" if u is None else u, v) for u, v in alts if v >= 5e-7)      # not one that prints as 0
 
     with torch.no_grad(), open(os.path.join(outdir, "hyp-chars.txt"), "w") as fh, \
-            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw, alt_file as fha:
+            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw, alt_file as fha, kws_file as fhk:
         for x, _target, widths, _target_lens, meta in dataloader:
             out, lens = model(x.cuda(non_blocking=True), widths)
             if aligner is None and alternatives is None:
@@ -306,6 +313,13 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
                     words = aligner.words(al)
                     for w, (x0, x1) in zip(words, aligner.pixel_spans(words, int(widths[i]), int(lens[i]))):
                         fhw.write("%s\t%s\t%d\t%d\t%.6f\t%.6f\n" % (meta["utt-ids"][i], w.token, x0, x1, w.min_conf, w.mean_logp))
+            if fhk is not None:
+                hits = spotter.search(out, lens, keywords)
+                for i, q in zip(*np.nonzero((hits.expected_count >= min_count) & (hits.best_span[:, :, 0] >= 0))):
+                    first, last = int(hits.best_span[i, q, 0]), int(hits.best_span[i, q, 1])
+                    w, nf = int(widths[i]), int(lens[i])
+                    fhk.write("%s\t%s\t%.6f\t%.6f\t%d\t%d\n" % (meta["utt-ids"][i], kws_names[q], hits.expected_count[i, q],
+                                                               hits.best_logp[i, q], (first * w) // nf, -((-(last + 1) * w) // nf)))
             for i, hyp in enumerate(hyps):
                 hyp_utf8 = visual_to_logical(hyp) if visual_to_logical is not None else hyp
                 uttid = meta["utt-ids"][i]

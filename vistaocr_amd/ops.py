@@ -1424,3 +1424,53 @@ def ctc_edit_scores(logits, lens, labels, label_lens, canon=None):
     if squeeze:
         return ctc[:, 0], sub[:, 0], dele[:, 0], ins[:, 0]
     return ctc, sub, dele, ins
+
+
+def ctc_keyword_scores(logits, lens, queries, query_lens, query_flags=None, canon=None):
+    """CTC keyword search (vocr_ctc_keyword_scores) on raw logits [T,B,V]: for every (line, query) the natural log of the EXPECTED
+    NUMBER of occurrences of the query as a contiguous substring of the collapsed labelling - exact, over all frame paths; min(1, count)
+    bounds the probability that it occurs at all - and the best single occurrence.  `lens` as for ctc_align; `queries` int32 device
+    tensor [Q,L] (shared by all lines), `query_lens` int32 [Q], `query_flags` int32 [Q] or None (bit 0: only at the very beginning of the
+    labelling, bit 1: only at its end; both: ln P_ctc(query | x); bits 2 / 3 change only the reported span: it leaves out the frames of the
+    first / last label, which KeywordSpotter's whole-word search uses for its padding spaces); `canon` int32 [V] device tensor of the
+    symbol classes or None.
+    Returns, on the device, (log_count fp32 [B,Q]; best fp32 [B,Q] = the best occurrence's score; span int32 [B,Q,2] = its first and
+    last frame).  -inf / -inf / -1 where there is no occurrence and for an invalid query: length outside [1, L], a label <= 0 or >= V or
+    in the blank's class, or a trimmed query with no label left for the span (fewer than 2 labels with bit 2 or 3, fewer than 3 with
+    both)."""
+    _need_gpu(logits, queries, query_lens)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    dev = logits.device
+    if queries.dim() != 2 or queries.dtype != torch.int32 or query_lens.dtype != torch.int32 or query_lens.numel() != queries.shape[0] \
+            or query_lens.dim() != 1:
+        raise RuntimeError("ctc_keyword_scores: queries must be int32 [Q,L] and query_lens int32 [Q] (queries %s, query_lens %s)"
+                           % (tuple(queries.shape), tuple(query_lens.shape)))
+    queries, query_lens = queries.contiguous(), query_lens.contiguous()
+    Q, stride = int(queries.shape[0]), int(queries.shape[1])
+    nbytes = _lib.load().vocr_ctc_keyword_workspace_bytes(T, B, V, Q, stride) if Q >= 1 and stride >= 1 else 0
+    if nbytes == 0:
+        raise RuntimeError("ctc_keyword_scores: unsupported shape (T=%d B=%d V=%d Q=%d query length %d; 2 <= V <= 256, Q >= 1, "
+                           "1 <= query length <= 128, T * B * Q < 2^31)" % (T, B, V, Q, stride))
+    if query_flags is not None:
+        _need_gpu(query_flags)
+        if query_flags.dtype != torch.int32 or tuple(query_flags.shape) != (Q,):
+            raise RuntimeError("ctc_keyword_scores: query_flags must be int32 [Q]")
+        query_flags = query_flags.contiguous()
+    if torch.is_tensor(lens):
+        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    if lens_dev.numel() != B:
+        raise RuntimeError("ctc_keyword_scores: %d lengths for %d lines" % (lens_dev.numel(), B))
+    if canon is not None:
+        _need_gpu(canon)
+        if canon.dtype != torch.int32 or canon.numel() != V:
+            raise RuntimeError("ctc_keyword_scores: canon must be int32 [V]")
+    log_count = torch.empty(B, Q, dtype=torch.float32, device=dev)
+    best = torch.empty(B, Q, dtype=torch.float32, device=dev)
+    span = torch.empty(B, Q, 2, dtype=torch.int32, device=dev)
+    ws = _ws(nbytes, dev)
+    call("vocr_ctc_keyword_scores", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(queries), _p(query_lens), _p(query_flags), Q, stride,
+         stride, _p(log_count), _p(best), _p(span), _p(ws), ws.numel() * 4, _stream())
+    return log_count, best, span
