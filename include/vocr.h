@@ -547,6 +547,39 @@ int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens, int t, int
                             int max_query_len, float* out_log_count, float* out_best, int32_t* out_span,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- edit statistics: compute_cer_wer of test_on_val (src/textutils.py:264-351, src/train_cnn_lstm.py:32-100) and src/edit_dist_trace.py ---- */
+/* Levenshtein statistics (unit costs) of np (hypothesis, reference) pairs that are already on the device: distances and lengths over
+ * characters and over the tokens of form_tokenized_words, and - on request - the operation trace.  Integer arithmetic: every output
+ * equals the cell-by-cell DP's bit for bit.  A is ALWAYS the hypothesis side, B the reference side.  a_labels[na][a_stride],
+ * a_lens[na], b_labels[nb][b_stride], b_lens[nb] device int32: the layout the beam searches and vocr_greedy_collapse write ([B][n][T]
+ * is [B*n][T]); pairs[np][2] = {index into a, index into b}.  canon[V] as everywhere (NULL: identity): two labels are equal iff
+ * their classes are.  kinds[V] = vocr_ctc_word_beam_search's cls_kind (1 letter, 2 space, 3 single; read at the class): a run of
+ * letters is one word, every single a word of its own, anything else separates; two words are equal iff they have the same length
+ * and the same classes.  kinds = NULL: no word statistics (the word fields are -1; asking for words alone is then an error).
+ * want: bit 0 character statistics, bit 1 word statistics (at least one of the two), bit 2 the trace (needs bit 0): the operation
+ * counts of what bits 0 / 1 ask for, out_confusion and out_ops.  Without bit 2 only distances and lengths are produced and no back
+ * pointer is stored.  out_stats[np][12] = {char_dist, char_sub, char_ins, char_del, hyp_chars, ref_chars, word_dist, word_sub,
+ * word_ins, word_del, hyp_words, ref_words}; a field that was not asked for is -1; sub + ins + del = dist.  INS: a hypothesis
+ * element without a counterpart in the reference; DEL: a reference element missing from the hypothesis.  Trace tie rule
+ * (edit_dist_trace.py): at a cell take the diagonal (COPY when the elements are equal, else SUB) if its cost is <= both others,
+ * otherwise INS (from i-1) if its cost is <= DEL's, otherwise DEL (from j-1); the walk starts at (|A|, |B|) and is complete: at
+ * j = 0 the remaining i are INS, at i = 0 the remaining j are DEL.  out_confusion[V][V] (may be NULL; the caller zeroes it, the call
+ * ADDS to it with integer atomics): over the character trace of every pair, COPY and SUB at [reference class][hypothesis class],
+ * INS at [0][hypothesis class], DEL at [reference class][0].  out_ops[np][ops_stride] (may be NULL; ops_stride >= max_a_len +
+ * max_b_len): the character trace from the front, 1 COPY, 2 SUB, 3 INS, 4 DEL, 0 past its end (every byte of a row is written).
+ * A length of 0 is legal on either side.  A label <= 0 or >= v or in the blank's class, a length outside [0, max], or a pair index out
+ * of range makes every statistic of THAT pair -1 (and its row of out_ops 0); it adds nothing to the confusion.  Nothing past a
+ * sequence's length is read as content.  Results are bit-identical from run to run.  Limits: 2 <= v <= 256, na, nb, np >= 1,
+ * 0 <= max_a_len, max_b_len <= 2048, strides >= the maxima.  Workspace (with bit 2 and a pair table beyond the LDS share, 2 bits per
+ * cell: one slab per RESIDENT workgroup, at most 256 of them - it does not grow with np) from vocr_edit_stats_workspace_bytes (0 for an
+ * unsupported shape); an unsupported shape fails with VOCR_EINVAL before any launch. */
+size_t vocr_edit_stats_workspace_bytes(int na, int nb, int np, int v, int max_a_len, int max_b_len, int want);
+int vocr_edit_stats(const int32_t* a_labels, const int32_t* a_lens, int na, int a_stride, int max_a_len,
+                    const int32_t* b_labels, const int32_t* b_lens, int nb, int b_stride, int max_b_len,
+                    const int32_t* pairs, int np, const int32_t* canon, const int32_t* kinds, int v, int want,
+                    int32_t* out_stats, int32_t* out_confusion, uint8_t* out_ops, int ops_stride,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

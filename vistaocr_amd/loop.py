@@ -176,6 +176,42 @@ def test_on_val(val_dataloader, model, criterion):
     return loss_avg, cer_avg, wer_avg
 
 
+def test_on_val_device(val_dataloader, model, criterion):
+    """test_on_val with the scoring on the device: same contract, same return values, usable as fit(validate_fn=...).  The greedy
+    labels come from vocr_greedy_collapse and are scored against the batch's targets by ErrorScorer (vocr_edit_stats) without leaving
+    the device; one small device-to-host copy per batch brings the integers back.  The per-line CER / WER are the floats
+    compute_cer_wer returns for the same label strings (ErrorScorer.score says where a degenerate reference differs) and they enter
+    the same running means in the same order."""
+    from . import ops
+    from .score import ErrorScorer
+    scorer = ErrorScorer(model.alphabet)
+    thresh = np.float32(3 * 1 / len(model.alphabet))
+    cer_avg = wer_avg = loss_avg = 0.0
+    n = 0
+    model.eval()
+    with torch.no_grad():
+        for x, target, widths, target_lens, _ in val_dataloader:
+            out, lens = model(x.cuda(non_blocking=True), widths)
+            loss = criterion(out, target, lens, target_lens)
+            dev = out.device
+            idx, mx = ops.argmax_rows(out.detach())
+            lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+            labels, counts = ops.greedy_collapse(idx, mx, lens_dev, scorer.tables(dev)[0], thresh)
+            res = scorer.score(labels, counts, target, target_lens)
+            bsz = x.size(0)
+            n += 1
+            loss_avg += (float(loss) / bsz - loss_avg) / n
+            bc = bw = 0.0
+            for c, w in zip(res.cer.tolist(), res.wer.tolist()):
+                bc += c
+                bw += w
+            cer_avg += (bc / bsz - cer_avg) / n
+            wer_avg += (bw / bsz - wer_avg) / n
+    model.train()
+    _check_device_health(model)
+    return loss_avg, cer_avg, wer_avg
+
+
 def save_snapshot(path, iteration, model, optimizer, rtl, cur_lr, val_loss, val_cer, val_wer, line_height):
     """The checkpoint dictionary of src/train_cnn_lstm.py:427-438, readable by this build's and by the reference's
     FromSavedWeights: the alphabet is pickled under the reference's class path (checkpoint.save) and, for a model built
@@ -247,7 +283,7 @@ def _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataload
 
 
 def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, decoder=None, aligner=None, alternatives=None,
-                   spotter=None, keywords=None, min_count=0.5):
+                   spotter=None, keywords=None, min_count=0.5, scorer=None):
     """The inference driver of src/decode_testset.py:42-206 without the LM branch: forward every batch, greedy-decode,
     and write `hyp-chars.txt` ("<uxxxx ...> (<utt-id>)") and `hyp-chars.txt.utf8` ("<utf8> (<utt-id minus last _part>)").
     The reference runs the decode in a background process because its per-frame numpy argmax is slow; here the argmax
@@ -268,7 +304,15 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     (a list in the forms KeywordSpotter.search takes): with both, every line is searched for every keyword and `hyp-kws.tsv` is written
     as well, tab-separated: utt-id, keyword (as given; an index list joined by spaces), expected_count, best_logp, x0, x1 (input pixels
     of the best occurrence, CtcAligner.pixel_spans' geometry), one row for every (line, keyword) that has an occurrence at all and
-    whose expected count is at least `min_count`.  Without them (the default) nothing changes.  Returns the number of lines written."""
+    whose expected count is at least `min_count`.  Without them (the default) nothing changes.  `scorer` (a vistaocr_amd.ErrorScorer,
+    which says what its numbers are): with one, every hypothesis is scored, in the decoder's (visual) order, against the loader's targets
+    and two more files are written, tab-separated: `hyp-scores.tsv`, one row per line: utt-id, ref_chars, char_dist, sub, ins, del, cer,
+    ref_words, word_dist, wer, and a last row `TOTAL` with the corpus rates (summed distances over summed lengths); `confusions.tsv`:
+    ref, hyp, count (ErrorScorer.confusions of the matrix accumulated over all lines).  What is scored is the text of `hyp-chars.txt`: the decoder's uxxxx
+    strings go through ErrorScorer.score_strings, one small host-to-device copy per batch, so that every decoder this function drives
+    (greedy, the beam searches, an LM decoder on the host) is scored alike; a line that cannot be scored raises.  Without one (the
+    default) nothing changes.
+    Returns the number of lines written."""
     import contextlib
     import os
     from .textutils import utf8_to_uxxxx, uxxxx_to_utf8
@@ -281,6 +325,8 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
     words_file = open(os.path.join(outdir, "hyp-words.tsv"), "w") if aligner is not None else contextlib.nullcontext()
     alt_file = open(os.path.join(outdir, "hyp-chars-alt.tsv"), "w") if alternatives is not None else contextlib.nullcontext()
     kws_file = open(os.path.join(outdir, "hyp-kws.tsv"), "w") if spotter is not None and keywords is not None else contextlib.nullcontext()
+    score_file = open(os.path.join(outdir, "hyp-scores.tsv"), "w") if scorer is not None else contextlib.nullcontext()
+    score_sums, score_conf = np.zeros(12, dtype=np.int64), None
     kws_names = [k if isinstance(k, str) else " ".join(str(int(v)) for v in k) for k in keywords] if keywords is not None else []
     if alternatives is not None:
         from .align import CtcAligner
@@ -290,10 +336,11 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
         return "".join("\t%s:%.6f" % ("<del>" if u is None else u, v) for u, v in alts if v >= 5e-7)      # not one that prints as 0
 
     with torch.no_grad(), open(os.path.join(outdir, "hyp-chars.txt"), "w") as fh, \
-            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw, alt_file as fha, kws_file as fhk:
+            open(os.path.join(outdir, "hyp-chars.txt.utf8"), "w") as fh8, words_file as fhw, alt_file as fha, kws_file as fhk, \
+            score_file as fhs:
         for x, _target, widths, _target_lens, meta in dataloader:
             out, lens = model(x.cuda(non_blocking=True), widths)
-            if aligner is None and alternatives is None:
+            if aligner is None and alternatives is None and scorer is None:
                 hyps = model.decode_without_lm(out, lens, uxxxx=False) if decoder is None else decoder.decode(out, lens, uxxxx=False)
             else:
                 # the same hypotheses in uxxxx form (decode's utf8 is uxxxx_to_utf8 of them), aligned as they stand
@@ -313,6 +360,22 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
                     words = aligner.words(al)
                     for w, (x0, x1) in zip(words, aligner.pixel_spans(words, int(widths[i]), int(lens[i]))):
                         fhw.write("%s\t%s\t%d\t%d\t%.6f\t%.6f\n" % (meta["utt-ids"][i], w.token, x0, x1, w.min_conf, w.mean_logp))
+            if scorer is not None:
+                refs_ux = []
+                o = 0
+                for L in [int(v) for v in _target_lens]:
+                    refs_ux.append(" ".join(model.alphabet.idx_to_char[int(v)] for v in _target[o:o + L]))
+                    o += L
+                res = scorer.score_strings(hyps_ux, refs_ux, trace=True, device=out.device)
+                score_conf = res.confusion.astype(np.int64) if score_conf is None else score_conf + res.confusion
+                for i in range(len(hyps_ux)):
+                    row = np.array([f[i] for f in res[:12]], dtype=np.int64)
+                    if row[0] < 0 or row[6] < 0:                  # never a distance: it must not reach the sums
+                        raise RuntimeError("decode_dataset: the pair of %s could not be scored (a label outside the alphabet, the blank, "
+                                           "or a line of more than 2048 characters)" % meta["utt-ids"][i])
+                    score_sums += row
+                    fhs.write("%s\t%d\t%d\t%d\t%d\t%d\t%.6f\t%d\t%d\t%.6f\n" % (meta["utt-ids"][i], row[5], row[0], row[1], row[2],
+                                                                              row[3], res.cer[i], row[11], row[6], res.wer[i]))
             if fhk is not None:
                 hits = spotter.search(out, lens, keywords)
                 for i, q in zip(*np.nonzero((hits.expected_count >= min_count) & (hits.best_span[:, :, 0] >= 0))):
@@ -326,5 +389,12 @@ def decode_dataset(model, dataloader, outdir, visual_to_logical=None, seed=7, de
                 fh.write("%s (%s)\n" % (utf8_to_uxxxx(hyp_utf8), uttid))
                 fh8.write("%s (%s)\n" % (hyp_utf8, uttid[:uttid.rfind("_")]))
                 n += 1
+        if scorer is not None:
+            t = score_sums
+            fhs.write("TOTAL\t%d\t%d\t%d\t%d\t%d\t%.6f\t%d\t%d\t%.6f\n" % (t[5], t[0], t[1], t[2], t[3], t[0] / max(t[5], 1), t[11], t[6],
+                                                                         t[6] / max(t[11], 1)))
+            with open(os.path.join(outdir, "confusions.tsv"), "w") as fhc:
+                for ref, hyp, count in (scorer.confusions(score_conf) if score_conf is not None else ()):
+                    fhc.write("%s\t%s\t%d\n" % (ref, hyp, count))
     _check_device_health(model)
     return n

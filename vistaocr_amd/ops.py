@@ -1474,3 +1474,69 @@ def ctc_keyword_scores(logits, lens, queries, query_lens, query_flags=None, cano
     call("vocr_ctc_keyword_scores", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(queries), _p(query_lens), _p(query_flags), Q, stride,
          stride, _p(log_count), _p(best), _p(span), _p(ws), ws.numel() * 4, _stream())
     return log_count, best, span
+
+
+EDIT_CHARS, EDIT_WORDS, EDIT_TRACE = 1, 2, 4
+EDIT_LEN_MAX = 2048
+EDIT_FIELDS = ("char_dist", "char_sub", "char_ins", "char_del", "hyp_chars", "ref_chars",
+               "word_dist", "word_sub", "word_ins", "word_del", "hyp_words", "ref_words")
+
+
+def edit_stats(a_labels, a_lens, b_labels, b_lens, pairs, v, canon=None, kinds=None, want=EDIT_CHARS, confusion=None, ops=False):
+    """Edit statistics (vocr_edit_stats) of (hypothesis, reference) pairs on the device.  `a_labels` int32 device tensor [na,La] or
+    [B,n,La] (a beam search's out_labels goes in as it is: row b * n + q), `a_lens` int32 [na] or [B,n]: the HYPOTHESES; `b_labels`
+    int32 [nb,Lb], `b_lens` int32 [nb]: the REFERENCES; `pairs` int32 [np,2] = (row of a, row of b); `v` the alphabet's size; `canon`
+    int32 [v] (symbol classes) or None; `kinds` int32 [v] (lm.class_kinds) or None = no word statistics.  `want`: EDIT_CHARS |
+    EDIT_WORDS | EDIT_TRACE (the trace needs the characters).  `confusion`: None or an int32 [v,v] device tensor the call ADDS the
+    character trace's operations to (needs EDIT_TRACE); `ops`: also return the character trace (needs EDIT_TRACE).  Sequences may be
+    up to 2048 labels long (a wider label tensor is read up to that length; a longer sequence makes its pairs invalid).
+    Returns, on the device: stats int32 [np,12] in the order of EDIT_FIELDS (-1: not asked for; a whole row of -1: an invalid pair), and
+    with `ops` also uint8 [np, La' + Lb'] = the operations from the front, 1 COPY, 2 SUB, 3 INS, 4 DEL, 0 past the end."""
+    for name, t in (("a_labels", a_labels), ("a_lens", a_lens), ("b_labels", b_labels), ("b_lens", b_lens), ("pairs", pairs)):
+        if t.dtype != torch.int32:
+            raise RuntimeError("edit_stats: %s must be int32 (got %s)" % (name, t.dtype))
+    if a_labels.dim() == 3:
+        a_labels, a_lens = a_labels.reshape(-1, a_labels.shape[2]), a_lens.reshape(-1)
+    if a_labels.dim() != 2 or a_lens.dim() != 1 or a_lens.numel() != a_labels.shape[0] or a_labels.shape[0] < 1:
+        raise RuntimeError("edit_stats: a_labels must be int32 [na,L] or [B,n,L] and a_lens int32 [na] or [B,n] (a_labels %s, a_lens %s)"
+                           % (tuple(a_labels.shape), tuple(a_lens.shape)))
+    if b_labels.dim() != 2 or b_lens.dim() != 1 or b_lens.numel() != b_labels.shape[0] or b_labels.shape[0] < 1:
+        raise RuntimeError("edit_stats: b_labels must be int32 [nb,L] and b_lens int32 [nb] (b_labels %s, b_lens %s)"
+                           % (tuple(b_labels.shape), tuple(b_lens.shape)))
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+        raise RuntimeError("edit_stats: pairs must be int32 [np,2] with np >= 1 (got %s)" % (tuple(pairs.shape),))
+    want, v = int(want), int(v)
+    if not (want & (EDIT_CHARS | EDIT_WORDS)) or (want & ~7) or ((want & EDIT_TRACE) and not (want & EDIT_CHARS)):
+        raise RuntimeError("edit_stats: want=%d: EDIT_CHARS or EDIT_WORDS must be set and EDIT_TRACE needs EDIT_CHARS" % want)
+    if (want & EDIT_WORDS) and kinds is None:
+        raise RuntimeError("edit_stats: EDIT_WORDS needs kinds (lm.class_kinds)")
+    if (ops or confusion is not None) and not (want & EDIT_TRACE):
+        raise RuntimeError("edit_stats: ops and confusion need EDIT_TRACE")
+    _need_gpu(a_labels, a_lens, b_labels, b_lens, pairs)
+    dev = a_labels.device
+    for name, t in (("canon", canon), ("kinds", kinds)):
+        if t is not None:
+            _need_gpu(t)
+            if t.dtype != torch.int32 or t.numel() != v:
+                raise RuntimeError("edit_stats: %s must be int32 [v]" % name)
+    if confusion is not None:
+        _need_gpu(confusion)
+        if confusion.dtype != torch.int32 or tuple(confusion.shape) != (v, v) or not confusion.is_contiguous():
+            raise RuntimeError("edit_stats: confusion must be a contiguous int32 [v,v] tensor")
+    a_labels, a_lens, b_labels, b_lens, pairs = (t.contiguous() for t in (a_labels, a_lens, b_labels, b_lens, pairs))
+    na, sa = int(a_labels.shape[0]), int(a_labels.shape[1])
+    nb, sb = int(b_labels.shape[0]), int(b_labels.shape[1])
+    if sa == 0:                                             # nothing to point at: one unused label per sequence
+        a_labels, sa = torch.zeros(na, 1, dtype=torch.int32, device=dev), 1
+    if sb == 0:
+        b_labels, sb = torch.zeros(nb, 1, dtype=torch.int32, device=dev), 1
+    ma, mb, npairs = min(sa, EDIT_LEN_MAX), min(sb, EDIT_LEN_MAX), int(pairs.shape[0])
+    nbytes = _lib.load().vocr_edit_stats_workspace_bytes(na, nb, npairs, v, ma, mb, want)
+    if nbytes == 0:
+        raise RuntimeError("edit_stats: unsupported shape (na=%d nb=%d np=%d v=%d; 2 <= v <= 256)" % (na, nb, npairs, v))
+    stats = torch.empty(npairs, 12, dtype=torch.int32, device=dev)
+    out_ops = torch.empty(npairs, ma + mb, dtype=torch.uint8, device=dev) if ops else None
+    ws = _ws(nbytes, dev)
+    call("vocr_edit_stats", _p(a_labels), _p(a_lens), na, sa, ma, _p(b_labels), _p(b_lens), nb, sb, mb, _p(pairs), npairs, _p(canon),
+         _p(kinds), v, want, _p(stats), _p(confusion), _p(out_ops), ma + mb, _p(ws), ws.numel() * 4, _stream())
+    return (stats, out_ops) if ops else stats
