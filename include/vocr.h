@@ -220,6 +220,21 @@ size_t vocr_gemm_workspace_bytes(int m, int n, int k, int has_bias_or_relu);
 int vocr_gemm(int transa, int transb, int m, int n, int k,
               const float* a, int lda, const float* b, int ldb, float* c, int ldc,
               const float* bias, int relu, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* Which launch vocr_gemm (nprob = nseg = 1) or vocr_gemm_pair (mode 0: nprob = 2, nseg = 1; mode 1: nprob = 1, nseg = 2) takes for a call,
+ * answered by the planner the two entry points launch from; touches no device memory (256 CUs are assumed when no device is visible).
+ * aligned: bit 0 = a and b are 16-byte aligned, bit 1 = c and the biases are (3: every pointer).  workspace_bytes: what a 16-byte aligned
+ * workspace holds (0: NULL).  tiles_only: vocr_gemm_pair's co-scheduling hint (mode | 4).  plan[VOCR_GEMM_PLAN_INTS]:
+ *   [0] kernel: 0 / 1 / 2 = tile kernel with 64x64 / 128x64 / 128x128 tiles, 3 = DMA-staged panel kernel
+ *   [1] 16-byte operand loads (1) or 4-byte ones (0; the panel kernel only has the 16-byte form)
+ *   tile kernel:  [2] whole tiles that lead the launch (0: every tile is cut along K), [3] K pieces per cut tile (1: nothing is cut),
+ *                 [4] k per piece
+ *   panel kernel: [5] column panels, [6] row groups, [7] K splits (1: no slabs), [8] k per split, [9] the most 32-row tiles a group holds
+ *   [10] launches of the product kernel: 1, or 2 when vocr_gemm_pair falls back to two vocr_gemm calls ([0] .. [4] then describe a call
+ *        with the flags given here; ask for each call with nprob = nseg = 1 when their flags differ)
+ *   [11] bytes of workspace the launch uses (K slabs) */
+#define VOCR_GEMM_PLAN_INTS 12
+int vocr_gemm_plan(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int aligned, int has_bias_or_relu,
+                   int accumulate, size_t workspace_bytes, int nprob, int nseg, int tiles_only, int* plan);
 /* Two products of ONE shape in one launch — the two directions of a bidirectional nn.LSTM layer (cnnlstm.py:148-149,288-290):
  *   mode 0: c0 = op(a0) op(b0) (+bias0)(relu),  c1 = op(a1) op(b1) (+bias1)(relu)      (x W_ih^T of both directions: a0 == a1;
  *           the weight gradients dgates_dir^T x and dgates_dir^T h of both directions)

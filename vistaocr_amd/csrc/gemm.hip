@@ -487,6 +487,38 @@ bool gemm_tail_fill_enabled() {
     static const int on = VOCR_EXPERIMENT_INT("VOCR_GEMM_TAILFILL", 1);
     return on != 0;
 }
+
+// Which kernel a product runs on, and how it is cut: the ONE decision behind vocr_gemm, vocr_gemm_pair and vocr_gemm_plan.
+struct GemmRoute { bool panel, vec; vocr_dma_gemm::Plan dma; GemmPlan tile; };
+
+// ab_aligned / all_aligned: a and b / every pointer (c and the biases too) on 16 bytes.  ws_bytes: usable workspace (0 when it is NULL or
+// not 16-byte aligned).  nprob x nseg > 1 is vocr_gemm_pair's single launch: only the panel kernel has one, so `panel == false` then means
+// "two vocr_gemm calls" and the tile fields describe the first of them.  tiles_only: the co-scheduling hint.
+GemmRoute gemm_route(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, bool ab_aligned, bool all_aligned,
+                     bool has_epilogue, bool accumulate, size_t ws_bytes, int nprob, int nseg, bool tiles_only) {
+    GemmRoute r;
+    r.panel = false;
+    r.vec = false;
+    r.dma = vocr_dma_gemm::Plan{false, 0, 0, 1, 0, 0};
+    // large, aligned products: the DMA-staged panel kernel (gemm_dma.hip); `accumulate` only through its slab reduce
+    if (!tiles_only && all_aligned) {
+        const vocr_dma_gemm::Plan d = vocr_dma_gemm::plan(transa, transb, m, n, k, lda, ldb, ldc, nprob, nseg, false);
+        const bool ws_ok = d.ok && (d.ksplit == 1 || ws_bytes >= d.slab_bytes);
+        if (ws_ok && (!accumulate || d.ksplit > 1)) {
+            r.panel = true;
+            r.dma = d;
+        }
+    }
+    // K cuts need room for one tile-sized slab per piece; with less workspace there are fewer pieces, with none K is never cut
+    const long max_pieces_128 = (long)(ws_bytes / (128 * 128 * sizeof(float)));
+    r.tile = gemm_plan(m, n, k, has_epilogue, max_pieces_128, gemm_tail_fill_enabled());
+    r.vec = ab_aligned && lda % 4 == 0 && ldb % 4 == 0 && m % 4 == 0 && n % 4 == 0 && k % 4 == 0;
+    return r;
+}
+
+inline size_t gemm_usable_workspace(const void* workspace, size_t workspace_bytes) {
+    return (workspace && (((uintptr_t)workspace) & 15) == 0) ? workspace_bytes : 0;
+}
 }  // namespace
 
 extern "C" size_t vocr_gemm_workspace_bytes(int m, int n, int k, int has_bias_or_relu) {
@@ -521,38 +553,35 @@ extern "C" int vocr_gemm(int transa, int transb, int m, int n, int k, const floa
     VOCR_CHECK_ARG(a && b && c, "vocr_gemm: null pointer");
     VOCR_CHECK_ARG(lda >= (transa ? m : k) && ldb >= (transb ? k : n) && ldc >= n, "vocr_gemm: bad leading dimension");
     hipStream_t s = (hipStream_t)stream;
-    // large, aligned products: the DMA-staged panel kernel (gemm_dma.hip); `accumulate` only through its slab reduce
-    if (!g_gemm_tiles_only && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)bias)) & 15) == 0) {
-        const vocr_dma_gemm::Plan d = vocr_dma_gemm::plan(transa, transb, m, n, k, lda, ldb, ldc, 1, 1, false);
-        const bool ws_ok = d.ok && (d.ksplit == 1 || (workspace && (((uintptr_t)workspace) & 15) == 0 && workspace_bytes >= d.slab_bytes));
-        if (ws_ok && (!accumulate || d.ksplit > 1)) {
-            const float* aa[2] = {a, nullptr};
-            const float* bb[2] = {b, nullptr};
-            float* cc[2] = {c, nullptr};
-            const float* bs[2] = {d.ksplit > 1 ? nullptr : bias, nullptr};
-            vocr_dma_gemm::launch(d, transa, transb, m, n, k, aa, lda, bb, ldb, cc, ldc, bs, d.ksplit > 1 ? 0 : relu, 1, 1, (float*)workspace, s);
-            VOCR_CHECK_LAUNCH("vocr_gemm(dma)");
-            if (d.ksplit > 1) {
-                const int tiles = d.groups * d.panels;
-                splitk_reduce_kernel<<<tiles * 32, 256, 0, s>>>((const float*)workspace, c, m, n, ldc, 256, 128, 0, d.ksplit, d.panels, bias, relu, accumulate);
-                VOCR_CHECK_LAUNCH("vocr_gemm(dma, split-K reduce)");
-            }
-            return VOCR_OK;
+    const bool ab_aligned = ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0;
+    const bool all_aligned = ab_aligned && ((((uintptr_t)c) | ((uintptr_t)bias)) & 15) == 0;
+    const GemmRoute route = gemm_route(transa, transb, m, n, k, lda, ldb, ldc, ab_aligned, all_aligned, bias != nullptr || relu != 0,
+                                       accumulate != 0, gemm_usable_workspace(workspace, workspace_bytes), 1, 1, g_gemm_tiles_only);
+    if (route.panel) {
+        const vocr_dma_gemm::Plan& d = route.dma;
+        const float* aa[2] = {a, nullptr};
+        const float* bb[2] = {b, nullptr};
+        float* cc[2] = {c, nullptr};
+        const float* bs[2] = {d.ksplit > 1 ? nullptr : bias, nullptr};
+        vocr_dma_gemm::launch(d, transa, transb, m, n, k, aa, lda, bb, ldb, cc, ldc, bs, d.ksplit > 1 ? 0 : relu, 1, 1, (float*)workspace, s);
+        VOCR_CHECK_LAUNCH("vocr_gemm(dma)");
+        if (d.ksplit > 1) {
+            const int tiles = d.groups * d.panels;
+            splitk_reduce_kernel<<<tiles * 32, 256, 0, s>>>((const float*)workspace, c, m, n, ldc, 256, 128, 0, d.ksplit, d.panels, bias, relu, accumulate);
+            VOCR_CHECK_LAUNCH("vocr_gemm(dma, split-K reduce)");
         }
+        return VOCR_OK;
     }
     const long sam = transa ? 1 : lda, sak = transa ? lda : 1;
     const long sbk = transb ? 1 : ldb, sbn = transb ? ldb : 1;
-    // K cuts need room for one tile-sized slab per piece; with less workspace there are fewer pieces, with none K is never cut
-    const long max_pieces_128 = (workspace && (((uintptr_t)workspace) & 15) == 0) ? (long)(workspace_bytes / (128 * 128 * sizeof(float))) : 0;
-    const GemmPlan p = gemm_plan(m, n, k, bias != nullptr || relu != 0, max_pieces_128, gemm_tail_fill_enabled());
+    const GemmPlan& p = route.tile;
     const bool big = p.big, half = p.half;
     const int kps = p.kps;
     float* slab = p.pieces > 0 ? (float*)workspace : nullptr;
     dim3 grid(p.n_whole + p.pieces);
     const float* zp = gemm_zero_page();
     VOCR_CHECK_ARG(zp != nullptr, "vocr_gemm: no device zero page");
-    const bool vec = ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0 && m % 4 == 0 && n % 4 == 0 &&
-                     k % 4 == 0;
+    const bool vec = route.vec;
 #define VOCR_GEMM_ARGS transa, transb, grid, s, m, n, k, a, sam, sak, b, sbk, sbn, c, ldc, bias, relu, accumulate, kps, zp, slab, p.n_whole, p.ppt, p.tiles_n
     if (big && half) {
         if (vec) launch_cfg<128, 64, 64, 32, true>(VOCR_GEMM_ARGS);
@@ -587,28 +616,27 @@ extern "C" int vocr_gemm_pair(int mode, int transa, int transb, int m, int n, in
     hipStream_t s = (hipStream_t)stream;
     const uintptr_t al = ((uintptr_t)a0) | ((uintptr_t)a1) | ((uintptr_t)b0) | ((uintptr_t)b1) | ((uintptr_t)c0) | ((uintptr_t)c1) |
                          ((uintptr_t)bias0) | ((uintptr_t)bias1);
-    if ((al & 15) == 0 && !co_sched) {
-        const int nprob = mode ? 1 : 2, nseg = mode ? 2 : 1;
-        const vocr_dma_gemm::Plan d = vocr_dma_gemm::plan(transa, transb, m, n, k, lda, ldb, ldc, nprob, nseg, false);
-        const bool ws_ok = d.ok && (d.ksplit == 1 || (workspace && (((uintptr_t)workspace) & 15) == 0 && workspace_bytes >= d.slab_bytes));
-        if (ws_ok) {
-            const float* aa[2] = {a0, a1};
-            const float* bb[2] = {b0, b1};
-            float* cc[2] = {c0, c1};
-            const bool split = d.ksplit > 1;
-            const float* bs[2] = {split ? nullptr : bias0, split ? nullptr : bias1};
-            vocr_dma_gemm::launch(d, transa, transb, m, n, k, aa, lda, bb, ldb, cc, ldc, bs, split ? 0 : relu, nprob, nseg, (float*)workspace, s);
-            VOCR_CHECK_LAUNCH("vocr_gemm_pair(dma)");
-            if (split) {
-                const int tiles = d.groups * d.panels;
-                for (int p = 0; p < nprob; ++p) {
-                    const float* sl = (const float*)workspace + (size_t)p * tiles * d.ksplit * 256 * 128;
-                    splitk_reduce_kernel<<<tiles * 32, 256, 0, s>>>(sl, p ? c1 : c0, m, n, ldc, 256, 128, 0, d.ksplit, d.panels, p ? bias1 : bias0, relu, 0);
-                    VOCR_CHECK_LAUNCH("vocr_gemm_pair(dma, split-K reduce)");
-                }
+    const int nprob = mode ? 1 : 2, nseg = mode ? 2 : 1;
+    const GemmRoute route = gemm_route(transa, transb, m, n, k, lda, ldb, ldc, (al & 15) == 0, (al & 15) == 0, bias0 != nullptr || relu != 0, false,
+                                       gemm_usable_workspace(workspace, workspace_bytes), nprob, nseg, co_sched);
+    if (route.panel) {
+        const vocr_dma_gemm::Plan& d = route.dma;
+        const float* aa[2] = {a0, a1};
+        const float* bb[2] = {b0, b1};
+        float* cc[2] = {c0, c1};
+        const bool split = d.ksplit > 1;
+        const float* bs[2] = {split ? nullptr : bias0, split ? nullptr : bias1};
+        vocr_dma_gemm::launch(d, transa, transb, m, n, k, aa, lda, bb, ldb, cc, ldc, bs, split ? 0 : relu, nprob, nseg, (float*)workspace, s);
+        VOCR_CHECK_LAUNCH("vocr_gemm_pair(dma)");
+        if (split) {
+            const int tiles = d.groups * d.panels;
+            for (int p = 0; p < nprob; ++p) {
+                const float* sl = (const float*)workspace + (size_t)p * tiles * d.ksplit * 256 * 128;
+                splitk_reduce_kernel<<<tiles * 32, 256, 0, s>>>(sl, p ? c1 : c0, m, n, ldc, 256, 128, 0, d.ksplit, d.panels, p ? bias1 : bias0, relu, 0);
+                VOCR_CHECK_LAUNCH("vocr_gemm_pair(dma, split-K reduce)");
             }
-            return VOCR_OK;
         }
+        return VOCR_OK;
     }
     // shapes the panel kernel does not take (or the co-scheduling hint): two calls of the tile kernel (mode 1: the second one
     // accumulates, the ReLU comes last)
@@ -621,6 +649,42 @@ extern "C" int vocr_gemm_pair(int mode, int transa, int transb, int m, int n, in
     int rc = vocr_gemm(transa, transb, m, n, k, a0, lda, b0, ldb, c0, ldc, bias0, 0, 0, workspace, workspace_bytes, stream);
     if (rc != VOCR_OK) return rc;
     return vocr_gemm(transa, transb, m, n, k, a1, lda, b1, ldb, c0, ldc, nullptr, relu, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vocr_gemm_plan(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int aligned, int has_bias_or_relu,
+                              int accumulate, size_t workspace_bytes, int nprob, int nseg, int tiles_only, int* plan) {
+    VOCR_CHECK_ARG(plan != nullptr, "vocr_gemm_plan: null pointer");
+    VOCR_CHECK_ARG(m > 0 && n > 0 && k > 0, "vocr_gemm_plan: bad shape m=%d n=%d k=%d", m, n, k);
+    VOCR_CHECK_ARG(lda >= (transa ? m : k) && ldb >= (transb ? k : n) && ldc >= n, "vocr_gemm_plan: bad leading dimension");
+    VOCR_CHECK_ARG((nprob == 1 && nseg == 1) || (nprob == 2 && nseg == 1) || (nprob == 1 && nseg == 2),
+                   "vocr_gemm_plan: nprob x nseg must be 1 x 1 (vocr_gemm), 2 x 1 or 1 x 2 (vocr_gemm_pair mode 0 / 1)");
+    VOCR_CHECK_ARG(nprob * nseg == 1 || !accumulate, "vocr_gemm_plan: vocr_gemm_pair does not accumulate");
+    const GemmRoute r = gemm_route(transa, transb, m, n, k, lda, ldb, ldc, (aligned & 1) != 0, (aligned & 3) == 3, has_bias_or_relu != 0,
+                                   accumulate != 0, workspace_bytes, nprob, nseg, tiles_only != 0);
+    for (int i = 0; i < VOCR_GEMM_PLAN_INTS; ++i) plan[i] = 0;
+    if (r.panel) {
+        const vocr_dma_gemm::Plan& d = r.dma;
+        const int mt = vocr_cdiv(m, 32);
+        plan[0] = 3;
+        plan[1] = 1;
+        plan[5] = d.panels;
+        plan[6] = d.groups;
+        plan[7] = d.ksplit;
+        plan[8] = d.kps;
+        plan[9] = d.ksplit > 1 ? (mt < 8 ? mt : 8) : mt / d.groups + (mt % d.groups ? 1 : 0);
+        plan[10] = 1;
+        plan[11] = (int)d.slab_bytes;
+        return VOCR_OK;
+    }
+    const GemmPlan& p = r.tile;
+    plan[0] = p.big ? (p.half ? 1 : 2) : 0;
+    plan[1] = r.vec ? 1 : 0;
+    plan[2] = p.n_whole;
+    plan[3] = p.ppt;
+    plan[4] = p.kps;
+    plan[10] = nprob * nseg;
+    plan[11] = (int)((size_t)p.pieces * p.bm * p.bn * sizeof(float));
+    return VOCR_OK;
 }
 
 namespace {

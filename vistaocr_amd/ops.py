@@ -47,6 +47,7 @@ def _f32c(t):
 
 
 # ---- side stream: weight-gradient GEMMs of an LSTM layer run concurrently with the next (latency-bound) sweep
+import ctypes as _ctypes
 import os as _os
 
 
@@ -680,6 +681,25 @@ def gemm(ta, tb, m, n, k, a, lda, b, ldb, c, ldc, bias=None, relu=False, accumul
     ws = _ws(nb, c.device) if nb else None
     call("vocr_gemm", int(ta), int(tb), m, n, k, _p(a), lda, _p(b), ldb, _p(c), ldc, _p(bias), int(relu), int(accumulate),
          _p(ws), nb, _stream())
+
+
+GEMM_PLAN_KERNELS = ("tile64x64", "tile128x64", "tile128x128", "panel")
+
+
+def gemm_plan(ta, tb, m, n, k, lda, ldb, ldc, aligned=3, epilogue=False, accumulate=False, workspace_bytes=None, nprob=1, nseg=1,
+              tiles_only=False):
+    """The launch vocr_gemm / vocr_gemm_pair takes for a call (include/vocr.h: vocr_gemm_plan), as a dict; no device memory is touched.
+    workspace_bytes None = what gemm() / gemm_pair() pass (the library's own size answer)."""
+    lib = _lib.load()
+    if workspace_bytes is None:
+        workspace_bytes = (lib.vocr_gemm_workspace_bytes(m, n, k, int(bool(epilogue))) if nprob * nseg == 1 else
+                           lib.vocr_gemm_pair_workspace_bytes(m, n, k, int(nseg == 2)))
+    out = (_ctypes.c_int * 12)()
+    call("vocr_gemm_plan", int(ta), int(tb), m, n, k, lda, ldb, ldc, int(aligned), int(bool(epilogue)), int(bool(accumulate)),
+         int(workspace_bytes), int(nprob), int(nseg), int(bool(tiles_only)), out)
+    v = list(out)
+    return dict(kernel=GEMM_PLAN_KERNELS[v[0]], vec=bool(v[1]), n_whole=v[2], pieces_per_tile=v[3], k_per_piece=v[4], panels=v[5],
+                groups=v[6], ksplit=v[7], k_per_split=v[8], max_row_tiles=v[9], launches=v[10], workspace_bytes=v[11])
 
 
 def gemm_pair(mode, ta, tb, m, n, k, a0, a1, lda, b0, b1, ldb, c0, c1, ldc, bias0=None, bias1=None, relu=False):
