@@ -319,6 +319,10 @@ int vocr_lstm_bias_from_parts(float* dbias, const void* workspace, int t, int b,
 /* Every fp32 operand element is written as a0 + a1 + a2 (three bf16 values whose sum is the fp32 value exactly) and a product is accumulated in fp32
  * from the six partial products of order <= 2^-16; the three dropped ones are <= 2^-23 |a b| (one unit roundoff of an fp32 product).
  * v_mfma_f32_32x32x16_bf16 runs at 16x the rate of the f32 MFMA: six per product = 2.67x the f32 matrix peak.
+ * Domain of "exactly": every finite |a| >= 2^-110, the top of the range included (from 2^127 (2 - 2^-8) up, where rounding a0 to nearest would
+ * overflow bf16, a0 is taken by truncation).  Below 2^-110 the last plane is a bf16 denormal, whose step 2^-133 is coarser than the operand's: the
+ * planes sum to a rounded to a multiple of 2^-133, |error| <= 2^-134 (fp32 denormals included; the conversions and the matrix pipe keep denormals -
+ * tests/test_x6_fp64_gpu.py pins both ends).  Inf and NaN stay non-finite in the planes and poison their output row / column.
  * vocr_gemm_x6_split writes the three planes of an operand in MFMA-fragment order (vocr_gemm_x6_planes_bytes(rows, k) bytes; rows padded to 256, K to
  * 32): x is [rows][k] with leading dimension ld (k_contiguous = 1) or [k][rows] (k_contiguous = 0: the transposed operands of the weight
  * gradients).  vocr_gemm_x6: C[m][n] = A[m][k] . B[n][k]^T (+ bias)(relu) from the planes of A and B, both outputs with ldc.  What is left of the
@@ -331,6 +335,16 @@ size_t vocr_gemm_x6_planes_bytes(int rows, int k);
 int vocr_gemm_x6_split(const float* x, const float* x2, int seg, int seg_axis, const float* mask, long ld, int rows, int k, int k_contiguous,
                        void* planes, void* stream);
 size_t vocr_gemm_x6_workspace_bytes(int m, int n, int k);
+/* Which launches vocr_gemm_x6 / vocr_gemm_h3 (b_row0_2 < 0) or their _two_views forms (b_row0_2 = the second view's b_row0) make for a product, answered
+ * by the planner they launch from; the plan does not depend on the split scheme.  Touches no device memory (256 CUs are assumed when no device is
+ * visible).  b_rows: the rows B's plane set was written for; has_workspace: 0 = the call passes workspace NULL.  plan[VOCR_GEMM_X6_PLAN_INTS]:
+ *   [0] 32-column tiles per workgroup tile: 4 (256 x 128) or 8 (256 x 256)      [1] workgroup tiles of the product
+ *   [2] tiles of the launch that runs the whole K (0: none)                     [3] tiles of the launch that is cut along K (0: no cut)
+ *   [4] K splits that launch runs (1: no cut)                                   [5] k16 stages per split (the last split may be shorter)
+ *   [6] 1 if the 256 x 256 tile was admissible (every 8-tile block it reads exists in B's plane set)
+ *   [7] the CU count the plan was made for                                      [8] bytes of workspace the K-cut launch uses */
+#define VOCR_GEMM_X6_PLAN_INTS 9
+int vocr_gemm_x6_plan(int m, int n, int k, int b_rows, int b_row0, int b_row0_2, int has_workspace, int* plan);
 /* A = rows a_row0 .. + m and k16 steps a_kk0 .. + k/16 of a plane set written for (a_rows, a_k) - a view: the row-shifted operands of the recurrent
  * weight gradient are k windows of ONE plane set -; B likewise (its rows are the output columns).  Two outputs: columns >= csplit go to c1 at
  * col - csplit, or rows >= rsplit to c1 at row - rsplit (<= 0: no cut). */

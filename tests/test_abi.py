@@ -132,6 +132,11 @@ def test_argument_validation_without_gpu():
     tv = lambda fn, *a: fn(one, 512, 64, 0, one, 128, 64, 512, 128, 64, *a)
     assert tv(lib.vocr_gemm_x6_two_views, 100, 0, 0, 0, 0, 0, 0, one, one, 128, None, None) == -1 and b"256-row tile" in lib.vocr_last_error()
     assert tv(lib.vocr_gemm_h3_two_views, 256, 0, 0, 0, 9, 0, 0, one, one, 128, None, None) == -1 and b"second view" in lib.vocr_last_error()
+    # the planner query: 8448 x 1024 x 512 on 256 CUs = one whole round of narrow tiles + 8 tiles cut four ways
+    out = (ctypes.c_int * 9)()
+    assert lib.vocr_gemm_x6_plan(8448, 1024, 512, 1024, 0, -1, 1, out) == 0 and list(out)[:7] == [4, 264, 256, 8, 4, 8, 1]
+    assert lib.vocr_gemm_x6_plan(256, 128, 40, 128, 0, -1, 1, out) == -1 and b"vocr_gemm_x6_plan" in lib.vocr_last_error()
+    assert lib.vocr_gemm_x6_plan(256, 128, 64, 128, 0, -1, 1, None) == -1
     # the opt-in fp16x3 split: two planes + the rows' maxima (fp32) behind them; the same validation in front of any launch
     assert lib.vocr_gemm_h3_planes_bytes(9408, 1024) == 2 * (37 * 8) * (32 * 2) * 1024 + 37 * 8 * 32 * 4 and lib.vocr_gemm_h3_planes_bytes(0, 8) == 0
     assert lib.vocr_gemm_h3_split(one, None, 8, 0, None, 64, 32, 64, 1, 0.0, one, None) == -1 and b"second piece" in lib.vocr_last_error()

@@ -44,15 +44,9 @@ def test_the_split_is_exact(dev):
     rows, k = 70, 48
     x = _rnd(g, dev, rows, k, a=2.0) * torch.pow(10.0, _rnd(g, dev, rows, k, a=30.0))
     buf = _planes(x, rows, k, True, k)
-    RT, KK = 8, 4
-    p = buf.view(torch.bfloat16).view(3, RT, KK, 64, 8).float().cpu()                    # [plane][row tile][k16 step][lane][8]
-    rec = torch.zeros(RT * 32, KK * 16, dtype=torch.float64)
-    for lane in range(64):
-        r, h = lane & 31, lane >> 5
-        blk = p[:, :, :, lane, :].double().sum(0)                    # [RT][KK][8]
-        for rt in range(RT):
-            for kk in range(KK):
-                rec[32 * rt + r, 16 * kk + 8 * h: 16 * kk + 8 * h + 8] = blk[rt, kk]
+    from tests import x6_ref
+    rec = x6_ref.decode(buf, "bf16x6", rows, k)[0].sum(0)               # [padded rows][padded k], fragment order undone
+    assert rec.shape == (256, 64)
     assert torch.equal(rec[:rows, :k].float(), x.cpu()), "the three planes do not sum to the operand"
     assert float(rec[rows:].abs().max()) == 0.0 and float(rec[:, k:].abs().max()) == 0.0                  # padding is zeros
 
@@ -67,18 +61,12 @@ def test_the_fp16x3_split_represents_its_operand(dev, kc):
     x[5] = 0.0                                                                            # an all-zero row
     src = x if kc else x.t().contiguous()
     buf = _planes(src, rows, k, kc, src.stride(0), scheme="fp16x3")
+    from tests import x6_ref
     RT, KK = 8, 14
-    nb = 2 * RT * KK * 64 * 8
-    p = buf[:nb].view(torch.float16).view(2, RT, KK, 64, 8).double().cpu()
-    amax = buf[nb:].view(torch.float32).cpu()
+    planes, amax = x6_ref.decode(buf, "fp16x3", rows, k)
     assert amax.numel() == RT * 32 and torch.equal(amax[:rows], x.abs().max(1).values.cpu()) and float(amax[rows:].abs().max()) == 0.0
-    rec = torch.zeros(RT * 32, KK * 16, dtype=torch.float64)
-    for lane in range(64):
-        r, h = lane & 31, lane >> 5
-        blk = p[:, :, :, lane, :].sum(0)
-        for rt in range(RT):
-            for kk in range(KK):
-                rec[32 * rt + r, 16 * kk + 8 * h: 16 * kk + 8 * h + 8] = blk[rt, kk]
+    rec = planes.sum(0)
+    assert rec.shape == (RT * 32, KK * 16)
     xd = x.double().cpu()
     am = amax[:rows].double().unsqueeze(1)
     e = torch.floor(torch.log2(torch.clamp(am, min=1e-300)))

@@ -68,6 +68,7 @@ SIGNATURES = {
     "vocr_gemm_x6_planes_bytes": (Z, [I, I]),
     "vocr_gemm_x6_split": (I, [P, P, I, I, P, ctypes.c_long, I, I, I, P, P]),
     "vocr_gemm_x6_workspace_bytes": (Z, [I, I, I]),
+    "vocr_gemm_x6_plan": (I, [I, I, I, I, I, I, I, P]),
     "vocr_gemm_x6": (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, P, P, I, I, I, P, P, I, P, P]),
     "vocr_gemm_x6_two_views": (I, [P, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, P]),
     "vocr_gemm_h3_two_views": (I, [P, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, I, P, P]),

@@ -1,6 +1,6 @@
 // fp32 GEMM on the bf16 matrix pipe by exact operand splitting ("bf16x6"): every fp32 operand element a is written as a0 + a1 + a2 with
 // a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1) - EXACT (3 x 8 significant bits cover fp32's 24; the residuals are computed in
-// fp32 without rounding) - and a*b is accumulated from the six partial products of order <= 2^-16 (a0b0, a0b1, a1b0, a0b2, a2b0, a1b1),
+// fp32 without rounding; for which magnitudes: include/vocr.h) - and a*b is accumulated from the six partial products of order <= 2^-16 (a0b0, a0b1, a1b0, a0b2, a2b0, a1b1),
 // each of them exact in the fp32 accumulator's input (8 x 8 bits); the three dropped ones (a1b2, a2b1, a2b2) are <= 2^-23 |a b|, one unit
 // roundoff of the fp32 product the f32 MFMA would have formed.  v_mfma_f32_32x32x16_bf16 runs at 16x the rate of v_mfma_f32_32x32x2_f32, so six
 // of them per product are 2.67x the f32 matrix peak (417 TFLOP/s of fp32-equivalent work on an MI355X).
@@ -32,6 +32,8 @@ constexpr int X6_LDS = 144 * 1024;                  // the ring: 4 x 36 KB (256 
 
 __device__ __forceinline__ void split3(float a, __bf16& b0, __bf16& b1, __bf16& b2) {
     b0 = (__bf16)a;
+    // |a| >= 2^127 (2 - 2^-8) rounds UP to bf16's infinity: take the first plane by truncation there (the residual, 16 bits, still fits two planes exactly)
+    if (__builtin_isinf((float)b0) && !__builtin_isinf(a)) b0 = __builtin_bit_cast(__bf16, (unsigned short)(__float_as_uint(a) >> 16));
     const float r1 = a - (float)b0;
     b1 = (__bf16)r1;
     const float r2 = r1 - (float)b1;
@@ -552,21 +554,38 @@ X6Plan x6_plan(int nct, int m, int n, int nkk, int ncu, bool can_cut) {
     return p;
 }
 
+// What a product launches: the ONE decision behind vocr_gemm_x6 / _h3 (and their two-view forms) and vocr_gemm_x6_plan.  b_rt0 / b_rt0_alt: the 32-row
+// tile B's view(s) start at, RTb: B's plane set's row tiles.  The wide tile reads whole blocks of 8 column tiles: they must exist in B's plane set (rows
+// padded to 256: always, unless a view starts late).
+struct X6Route { X6Plan p; bool wide_ok; int ncu, main_tiles, cut_tiles, ksplit, stages_per_split; size_t ws_bytes; };
+X6Route x6_route(int m, int n, int nkk, int RTb, int b_rt0, int b_rt0_alt, bool can_cut) {
+    X6Route r;
+    r.ncu = x6_cu_count();
+    const X6Plan p4 = x6_plan(4, m, n, nkk, r.ncu, can_cut), p8 = x6_plan(8, m, n, nkk, r.ncu, can_cut);
+    r.wide_ok = b_rt0 + 8 * p8.ntiles <= RTb && b_rt0_alt + 8 * p8.ntiles <= RTb;
+    r.p = (r.wide_ok && p8.cost < p4.cost) ? p8 : p4;
+    r.main_tiles = r.p.ks > 1 ? r.p.full : r.p.tiles;
+    r.cut_tiles = r.p.ks > 1 ? r.p.rem : 0;
+    r.stages_per_split = r.p.ks > 1 ? vocr_cdiv(nkk, r.p.ks) : nkk;
+    r.ksplit = vocr_cdiv(nkk, r.stages_per_split);
+    r.ws_bytes = r.p.ks > 1 ? (size_t)r.ksplit * r.cut_tiles * X6_BM * (32 * r.p.nct) * sizeof(float) : 0;
+    return r;
+}
+
 template <int NCT, int NP>
-void x6_launch(X6Args g, const X6Plan& p, void* workspace, hipStream_t s) {
-    g.ntiles = p.ntiles;
-    const int main_tiles = p.ks > 1 ? p.full : p.tiles;
-    if (main_tiles > 0) {
-        g.tile0 = 0; g.ntile_launch = main_tiles; g.ksplit = 1; g.stages_per_split = g.nkk; g.slab = nullptr;
-        gemm_x6_kernel<NCT, NP><<<main_tiles, 512, X6_LDS, s>>>(g);
+void x6_launch(X6Args g, const X6Route& r, void* workspace, hipStream_t s) {
+    g.ntiles = r.p.ntiles;
+    if (r.main_tiles > 0) {
+        g.tile0 = 0; g.ntile_launch = r.main_tiles; g.ksplit = 1; g.stages_per_split = g.nkk; g.slab = nullptr;
+        gemm_x6_kernel<NCT, NP><<<r.main_tiles, 512, X6_LDS, s>>>(g);
     }
-    if (p.ks > 1) {
-        g.tile0 = p.full; g.ntile_launch = p.rem;
-        g.stages_per_split = vocr_cdiv(g.nkk, p.ks);
-        g.ksplit = vocr_cdiv(g.nkk, g.stages_per_split);
+    if (r.cut_tiles > 0) {
+        g.tile0 = r.main_tiles; g.ntile_launch = r.cut_tiles;
+        g.stages_per_split = r.stages_per_split;
+        g.ksplit = r.ksplit;
         g.slab = (float*)workspace;
-        gemm_x6_kernel<NCT, NP><<<p.rem * g.ksplit, 512, X6_LDS, s>>>(g);
-        gemm_x6_reduce_kernel<NCT><<<p.rem * (NCT == 4 ? 32 : 64), 256, 0, s>>>(g);
+        gemm_x6_kernel<NCT, NP><<<r.cut_tiles * r.ksplit, 512, X6_LDS, s>>>(g);
+        gemm_x6_reduce_kernel<NCT><<<r.cut_tiles * (NCT == 4 ? 32 : 64), 256, 0, s>>>(g);
     }
 }
 }  // namespace
@@ -605,11 +624,8 @@ static int x6_gemm_impl(const char* name, const void* a_planes, int a_rows, int 
     // fp16x3: the rows' maxima behind the planes
     g.sa = NP == 2 ? (const float*)((const unsigned char*)a_planes + (size_t)NP * g.RTa * g.KKa * 1024) : nullptr;
     g.sb = NP == 2 ? (const float*)((const unsigned char*)b_planes + (size_t)NP * g.RTb * g.KKb * 1024) : nullptr;
-    const int ncu = x6_cu_count();
-    const X6Plan p4 = x6_plan(4, m, n, g.nkk, ncu, workspace != nullptr), p8 = x6_plan(8, m, n, g.nkk, ncu, workspace != nullptr);
-    // the wide tile reads whole blocks of 8 column tiles: they must exist in B's plane set (rows padded to 256: always, unless a view starts late)
-    const bool wide_ok = g.b_rt0 + 8 * p8.ntiles <= g.RTb && g.b_rt0_alt + 8 * p8.ntiles <= g.RTb;
-    const X6Plan& p = (wide_ok && p8.cost < p4.cost) ? p8 : p4;
+    const X6Route route = x6_route(m, n, g.nkk, g.RTb, g.b_rt0, g.b_rt0_alt, workspace != nullptr);
+    const X6Plan& p = route.p;
     // a tile reads whole 256-row / (32 NCT)-column blocks of fragments: they must exist in the plane sets (zero padding or later rows)
     VOCR_CHECK_ARG(g.a_rt0 + 8 * g.mtiles <= g.RTa && g.b_rt0 + p.nct * p.ntiles <= g.RTb && g.a_kk0 + g.nkk <= g.KKa && g.b_kk0 + g.nkk <= g.KKb,
                    "%s: the view leaves its plane set", name);
@@ -624,9 +640,26 @@ static int x6_gemm_impl(const char* name, const void* a_planes, int a_rows, int 
         }
         lds_ok = true;
     }
-    if (p.nct == 8) x6_launch<8, NP>(g, p, workspace, (hipStream_t)stream);
-    else x6_launch<4, NP>(g, p, workspace, (hipStream_t)stream);
+    if (p.nct == 8) x6_launch<8, NP>(g, route, workspace, (hipStream_t)stream);
+    else x6_launch<4, NP>(g, route, workspace, (hipStream_t)stream);
     VOCR_CHECK_LAUNCH(name);
+    return VOCR_OK;
+}
+
+extern "C" int vocr_gemm_x6_plan(int m, int n, int k, int b_rows, int b_row0, int b_row0_2, int has_workspace, int* plan) {
+    VOCR_CHECK_ARG(plan != nullptr, "vocr_gemm_x6_plan: null pointer");
+    VOCR_CHECK_ARG(m > 0 && n > 0 && k > 0 && k % 16 == 0 && b_rows > 0, "vocr_gemm_x6_plan: bad shape (k %% 16 == 0)");
+    VOCR_CHECK_ARG(b_row0 >= 0 && b_row0 % 32 == 0 && (b_row0_2 < 0 || b_row0_2 % 32 == 0), "vocr_gemm_x6_plan: views start on tile boundaries");
+    const X6Route r = x6_route(m, n, k / 16, x6_rt(b_rows), b_row0 / 32, (b_row0_2 < 0 ? b_row0 : b_row0_2) / 32, has_workspace != 0);
+    plan[0] = r.p.nct;
+    plan[1] = r.p.tiles;
+    plan[2] = r.main_tiles;
+    plan[3] = r.cut_tiles;
+    plan[4] = r.ksplit;
+    plan[5] = r.stages_per_split;
+    plan[6] = r.wide_ok ? 1 : 0;
+    plan[7] = r.ncu;
+    plan[8] = (int)r.ws_bytes;
     return VOCR_OK;
 }
 

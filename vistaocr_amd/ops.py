@@ -770,6 +770,16 @@ def gemm_x6(a, a_rows, a_k, b, b_rows, b_k, m, n, k, c0, ldc, c1=None, csplit=0,
          int(k), _p(c0), _p(c1), int(csplit), int(rsplit), int(ldc), _p(bias0), _p(bias1), int(relu), _p(ws), _stream())
 
 
+def gemm_x6_plan(m, n, k, b_rows=None, b_row0=0, b_row0_2=-1, workspace=True):
+    """The launches gemm_x6 / gemm_x6_two_views make for a product (include/vocr.h: vocr_gemm_x6_plan; either split scheme), as a dict; no
+    device memory is touched.  b_rows None = a plane set written for exactly the n rows of the product."""
+    out = (_ctypes.c_int * 9)()
+    call("vocr_gemm_x6_plan", int(m), int(n), int(k), int(n if b_rows is None else b_rows), int(b_row0), int(b_row0_2), int(bool(workspace)), out)
+    v = list(out)
+    return dict(tile=v[0], tiles=v[1], whole_tiles=v[2], cut_tiles=v[3], ksplit=v[4], stages_per_split=v[5], wide_ok=bool(v[6]), cus=v[7],
+                workspace_bytes=v[8])
+
+
 def gemm_x6_two_views(a, a_rows, a_k, b, b_rows, b_k, m, n, k, rsplit, views0, views1, c0, c1, ldc, a_row0=0):
     """Two products of one shape in one launch (include/vocr.h: vocr_gemm_x6_two_views): rows < rsplit with views0 = (a_kk0, b_row0, b_kk0) into c0,
     rows >= rsplit with views1 into c1."""
