@@ -1,10 +1,11 @@
-"""GPU: the CTC criterion of ctc.hip (log-softmax, the three alpha/beta kernels, the gradient kernel) against the fp64 restatement of
+"""GPU: the CTC criterion of ctc.hip (log-softmax, the three alpha/beta launch paths, the gradient kernel) against the fp64 restatement of
 tests/ctc_ref.py, per line and per gradient element, under the bars derived there (tests/test_ctc_ref_cpu.py holds those bars to having
 teeth), and the greedy decode kernels against a plain host restatement, exactly.
 
-vocr_ctc_loss_grad picks its alpha/beta kernel from max_label_len alone (it only sizes the workspace rows): <= 31 the one-position-per-
-lane register kernel, <= 63 the two-positions-per-lane one, above that the generic LDS kernel.  ctc.hip promises that all three give the
-same bits; every batch here runs through each kernel that admits it and the results must be torch.equal.
+vocr_ctc_loss_grad picks its alpha/beta launch path from max_label_len alone (it only sizes the workspace rows): <= 31 the register kernel
+with one position per lane (ctc_alpha_beta_reg_kernel<1>), <= 63 the same with two (<2>), above that the LDS kernel
+(ctc_alpha_beta_lds_kernel).  ctc.hip promises that all three give the same bits; every batch here runs through each path that admits it
+and the results must be torch.equal.
 
 Every case prints e_k (the kernel's max abs error against fp64), e_32 (the fp32 restatement's) and the fraction of the bar each used -
 run with -s to see the table."""

@@ -720,7 +720,7 @@ def test_lstm_forward_step_ranges_resume_bit_exactly(dev, T, B, H, cut):
 
 
 @pytest.mark.parametrize("T,B,V,L", [(30, 4, 20, [5, 3, 1, 0]), (147, 8, 96, None), (60, 3, 166, [29, 10, 2]),
-                                     # 2L+1 in (64, 128]: two extended-label positions per lane (ctc_alpha_beta128_kernel) - the seam at position 64
+                                     # 2L+1 in (64, 128]: two extended-label positions per lane (ctc_alpha_beta_reg_kernel<2>) - the seam at position 64
                                      # crossed by odd and even label counts, a short line and an empty one beside the long ones; L = 63 fills all 127
                                      (150, 6, 166, [39, 32, 31, 33, 7, 0]), (140, 3, 96, [63, 62, 40]),
                                      # 2L+1 > 128: the generic LDS kernel

@@ -6,13 +6,11 @@
 // max-shifted log-sum-exp (the same formulation as the PyTorch-CPU criterion the parity target uses).
 //   kernel 1  row-wise log-softmax            : one wave per (t,b) row
 //   kernel 2  alpha and beta sweeps           : one wave per (sample, direction); lanes over s; the previous
-//                                               row lives in LDS
+//                                               row lives in registers (S <= 128) or in LDS
 //   kernel 3  gradient                        : one wave per (t,b); lanes over the alphabet
-#include "vocr_common.h"
+#include "ctc_math.h"
 
 namespace {
-
-constexpr float NEG_INF = -INFINITY;
 
 __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* __restrict__ x, float* __restrict__ lp,
                                                                int rows, int V) {
@@ -31,296 +29,177 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* __re
     for (int v = lane; v < V; v += 64) lr[v] = xr[v] - lse;
 }
 
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-    float m = fmaxf(a, fmaxf(b, c));
-    if (m == NEG_INF) return NEG_INF;
-    return logf(expf(a - m) + expf(b - m) + expf(c - m)) + m;
+// Alpha and beta of one sample in one body: beta is alpha of the reversed labelling over the reversed frames, so the beta wave
+// (blockIdx.x & 1) runs the alpha recursion in MIRRORED coordinates - position s' = S-1-s, frame t' = Tb-1-t, label lab[L-1-p'] - and
+// stores every value to its un-mirrored place in ab[b][dir][t][s].  The mirror is folded into wave-uniform bases and signed strides
+// computed once (a frame step of +-B*V in lp, a row step of +-SP in ab, a label step of +-1): the loops below have no direction
+// select, and both directions evaluate the same expressions in the same order per element as a hand-written beta would (the
+// neighbours s, s+1, s+2 of a beta step are s', s'-1, s'-2).  Columns s in [S, SP) of the rows t < Tb are written -inf by the lanes
+// whose s' >= S (they keep the identity column s = s'); rows t >= Tb are never written.
+struct Mirror {
+    int S, Tb;
+    int step, lab0, col0;      // +-1; the label under mirrored odd position s': lab[lab0 + step * (s' >> 1)]; the stored column of s' < S: col0 + step * s'
+    long fstep, rstep;         // frame t' of a column of lp: lp0[t' * fstep]; row t' of ab: out[t' * rstep]
+    const int32_t* lab;
+    const float* lp0;
+    float* out;
+    __device__ __forceinline__ int ext(int s) const { return (s >= 0 && s < S && (s & 1)) ? lab[lab0 + step * (s >> 1)] : 0; }
+    __device__ __forceinline__ int col(int s) const { return s < S ? col0 + step * s : s; }
+};
+
+__device__ __forceinline__ Mirror mirror_of(int b, int dirn, const float* __restrict__ lp, const int32_t* __restrict__ labels,
+                                            const int32_t* __restrict__ label_offsets, const int32_t* __restrict__ label_lens,
+                                            const int32_t* __restrict__ act_lens, float* __restrict__ ab, int T, int B, int V, int SP) {
+    Mirror m;
+    const int L = label_lens[b];
+    m.S = 2 * L + 1;
+    m.Tb = act_lens[b];
+    m.lab = labels + label_offsets[b];
+    m.step = dirn ? -1 : 1;
+    m.lab0 = dirn ? L - 1 : 0;
+    m.col0 = dirn ? m.S - 1 : 0;
+    const long tstride = (long)B * V;
+    const int t0 = dirn ? max(m.Tb - 1, 0) : 0;                    // the frame that t' = 0 stands for
+    m.fstep = dirn ? -tstride : tstride;
+    m.rstep = dirn ? -SP : SP;
+    m.lp0 = lp + (long)t0 * tstride + (long)b * V;
+    m.out = ab + ((long)(b * 2 + dirn) * T + t0) * SP;
+    return m;
 }
 
-// grid.x = 2*B (even: alpha of sample b, odd: beta); 64 threads.  ab[b][dir][t][s], row pitch SP.
-__global__ __launch_bounds__(64) void ctc_alpha_beta_kernel(const float* __restrict__ lp, const int32_t* __restrict__ labels,
-                                                            const int32_t* __restrict__ label_offsets,
-                                                            const int32_t* __restrict__ label_lens,
-                                                            const int32_t* __restrict__ act_lens, float* __restrict__ ab,
-                                                            float* __restrict__ nll, int T, int B, int V, int SP) {
-    extern __shared__ float sm[];            // [2][SP+2] rows (with 2 leading -inf pads) + int ext[SP]
+// grid.x = 2*B (even: alpha of sample b, odd: beta); 64 threads.  ab[b][dir][t][s], row pitch SP.  Any label length: lanes stride
+// over s', the previous row lives in LDS.
+__global__ __launch_bounds__(64) void ctc_alpha_beta_lds_kernel(const float* __restrict__ lp, const int32_t* __restrict__ labels,
+                                                                const int32_t* __restrict__ label_offsets,
+                                                                const int32_t* __restrict__ label_lens,
+                                                                const int32_t* __restrict__ act_lens, float* __restrict__ ab,
+                                                                float* __restrict__ nll, int T, int B, int V, int SP) {
+    extern __shared__ float sm[];            // [2][SP+4] rows (row[2 + s'], with 2 leading -inf pads) + int ext[SP]
     const int b = blockIdx.x >> 1, dirn = blockIdx.x & 1;
     const int lane = threadIdx.x;
-    const int L = label_lens[b], S = 2 * L + 1, Tb = act_lens[b];
-    const int32_t* lab = labels + label_offsets[b];
-    float* row0 = sm;
-    float* row1 = sm + (SP + 4);
-    int* ext = (int*)(sm + 2 * (SP + 4));
-    for (int s = lane; s < SP; s += 64) ext[s] = (s < S && (s & 1)) ? lab[s >> 1] : 0;
-    for (int s = lane; s < SP + 4; s += 64) { row0[s] = NEG_INF; row1[s] = NEG_INF; }
-    __syncthreads();
-    float* out = ab + ((long)(b * 2 + dirn) * T) * SP;
+    const Mirror m = mirror_of(b, dirn, lp, labels, label_offsets, label_lens, act_lens, ab, T, B, V, SP);
+    const int S = m.S, Tb = m.Tb;
     if (Tb <= 0) {
         if (dirn == 0 && lane == 0) nll[b] = (S == 1) ? 0.f : INFINITY;
         return;
     }
-    float* prev = row0;
-    float* cur = row1;
-    if (dirn == 0) {
-        // alpha_0
-        const float* l0 = lp + ((long)0 * B + b) * V;
+    float* prev = sm;
+    float* cur = sm + (SP + 4);
+    int* ext = (int*)(sm + 2 * (SP + 4));
+    for (int s = lane; s < SP; s += 64) ext[s] = m.ext(s);
+    for (int s = lane; s < SP + 4; s += 64) { prev[s] = NEG_INF; cur[s] = NEG_INF; }
+    __syncthreads();
+    for (int s = lane; s < SP; s += 64) {
+        float v = NEG_INF;
+        if (s == 0 || (s == 1 && S > 1)) v = m.lp0[ext[s]];
+        prev[2 + s] = v;
+        m.out[m.col(s)] = v;
+    }
+    __syncthreads();
+    for (int t = 1; t < Tb; ++t) {
+        const float* lt = m.lp0 + t * m.fstep;
+        float* ot = m.out + t * m.rstep;
         for (int s = lane; s < SP; s += 64) {
             float v = NEG_INF;
-            if (s == 0) v = l0[0];
-            else if (s == 1 && S > 1) v = l0[ext[1]];
-            prev[2 + s] = v;
-            out[s] = v;
+            if (s < S) {
+                const int e = ext[s];
+                const float a1 = prev[2 + s], a2 = prev[1 + s];
+                const float a3 = (s >= 2 && e != 0 && e != ext[s - 2]) ? prev[s] : NEG_INF;
+                const float l = lse3(a1, a2, a3);
+                v = (l == NEG_INF) ? NEG_INF : l + lt[e];
+            }
+            cur[2 + s] = v;
+            ot[m.col(s)] = v;
         }
         __syncthreads();
-        for (int t = 1; t < Tb; ++t) {
-            const float* lt = lp + ((long)t * B + b) * V;
-            for (int s = lane; s < SP; s += 64) {
-                float v = NEG_INF;
-                if (s < S) {
-                    const int e = ext[s];
-                    const float a1 = prev[2 + s], a2 = prev[1 + s];
-                    const float a3 = (s >= 2 && e != 0 && e != ext[s - 2]) ? prev[s] : NEG_INF;
-                    const float l = lse3(a1, a2, a3);
-                    v = (l == NEG_INF) ? NEG_INF : l + lt[e];
-                }
-                cur[2 + s] = v;
-                out[(long)t * SP + s] = v;
-            }
-            __syncthreads();
-            float* tmp = prev; prev = cur; cur = tmp;
-        }
-        if (lane == 0) {
-            const float a = prev[2 + S - 1];
-            const float c = S > 1 ? prev[2 + S - 2] : NEG_INF;
-            const float m = fmaxf(a, c);
-            nll[b] = (m == NEG_INF) ? INFINITY : -(logf(expf(a - m) + expf(c - m)) + m);
-        }
-    } else {
-        // beta_{Tb-1}; stored rows use the same [t][s] indexing; prev[s] holds beta[s], pads sit at S, S+1
-        const float* lT = lp + ((long)(Tb - 1) * B + b) * V;
-        for (int s = lane; s < SP + 2; s += 64) {
-            float v = NEG_INF;
-            if (s == S - 1) v = lT[0];
-            else if (s == S - 2 && S > 1) v = lT[ext[S - 2]];
-            prev[s] = v;
-            if (s < SP) out[(long)(Tb - 1) * SP + s] = v;
-        }
-        __syncthreads();
-        for (int t = Tb - 2; t >= 0; --t) {
-            const float* lt = lp + ((long)t * B + b) * V;
-            for (int s = lane; s < SP + 2; s += 64) {
-                float v = NEG_INF;
-                if (s < S) {
-                    const int e = ext[s];
-                    const float b1 = prev[s], b2 = prev[s + 1];
-                    const float b3 = (s + 2 < S && e != 0 && e != ext[s + 2]) ? prev[s + 2] : NEG_INF;
-                    const float l = lse3(b1, b2, b3);
-                    v = (l == NEG_INF) ? NEG_INF : l + lt[e];
-                }
-                cur[s] = v;
-                if (s < SP) out[(long)t * SP + s] = v;
-            }
-            __syncthreads();
-            float* tmp = prev; prev = cur; cur = tmp;
-        }
+        float* tmp = prev; prev = cur; cur = tmp;
     }
+    // -ln(alpha[S-1] + alpha[S-2]); S = 1: the second is a pad; +inf when neither end state is reachable
+    if (dirn == 0 && lane == 0) nll[b] = -lse2(prev[2 + S - 1], prev[2 + S - 2]);
 }
 
-// The same sweeps for S = 2L+1 <= 64 (L <= 31: every BASELINE workload): one extended-label position per lane, the previous
-// row stays in a register and neighbours are fetched with wave shuffles (no LDS, no barrier), and the one global operand of
-// a step, lp[t][b][l'_s], does not depend on the recursion, so it is gathered PF steps ahead.  The generic kernel paid an
-// L2/HBM round trip per time step for it (0.73 us x 294 steps = 215 us on the critical path of every training step).
-// Same expressions in the same order per element as ctc_alpha_beta_kernel: results are bit-identical.
-__global__ __launch_bounds__(64) void ctc_alpha_beta64_kernel(const float* __restrict__ lp, const int32_t* __restrict__ labels,
-                                                              const int32_t* __restrict__ label_offsets,
-                                                              const int32_t* __restrict__ label_lens,
-                                                              const int32_t* __restrict__ act_lens, float* __restrict__ ab,
-                                                              float* __restrict__ nll, int T, int B, int V) {
-    constexpr int SP = 64, PF = 8;
+// The same sweeps for S = 2L+1 <= 64 * NP with NP extended-label positions per lane, s' = lane + 64 * j: the previous row stays in
+// registers and neighbours are fetched with wave shuffles (no LDS, no barrier), and the one global operand of a step, lp[t][b][l'_s],
+// does not depend on the recursion, so it is gathered PF steps ahead.  Same expressions in the same order per element as
+// ctc_alpha_beta_lds_kernel: results are bit-identical.
+//   NP = 1 (L <= 31: every BASELINE workload).  The LDS kernel paid an L2/HBM round trip per time step for the gather (0.73 us x 294
+//          steps = 215 us on the critical path of every training step).
+//   NP = 2 (32 <= L <= 63: the long lines of BASELINE configs[3], ~1200 px with W / 30 labels): the seam between the halves is crossed
+//          with two broadcasts per step, lanes 0 and 1 of half j taking lanes 63 and 62 of half j-1.  The LDS kernel took 622 us for
+//          T = 576 (1.08 us per frame, chip otherwise idle: the backward waits for it); this one 136 us.
+template <int NP>
+__global__ __launch_bounds__(64) void ctc_alpha_beta_reg_kernel(const float* __restrict__ lp, const int32_t* __restrict__ labels,
+                                                                const int32_t* __restrict__ label_offsets,
+                                                                const int32_t* __restrict__ label_lens,
+                                                                const int32_t* __restrict__ act_lens, float* __restrict__ ab,
+                                                                float* __restrict__ nll, int T, int B, int V) {
+    constexpr int SP = 64 * NP, PF = 8;
     const int b = blockIdx.x >> 1, dirn = blockIdx.x & 1;
     const int lane = threadIdx.x;
-    const int L = label_lens[b], S = 2 * L + 1, Tb = act_lens[b];
-    const int32_t* lab = labels + label_offsets[b];
-    float* out = ab + ((long)(b * 2 + dirn) * T) * SP;
+    const Mirror m = mirror_of(b, dirn, lp, labels, label_offsets, label_lens, act_lens, ab, T, B, V, SP);
+    const int S = m.S, Tb = m.Tb;
     if (Tb <= 0) {
         if (dirn == 0 && lane == 0) nll[b] = (S == 1) ? 0.f : INFINITY;
         return;
     }
-    const bool in = lane < S;
-    const int e = (in && (lane & 1)) ? lab[lane >> 1] : 0;
-    const int e_m2 = __shfl_up(e, 2, 64), e_p2 = __shfl_down(e, 2, 64);
-    const float* col = lp + (long)b * V + e;              // lp[t][b][e] = col[t * B * V]
-    const long tstride = (long)B * V;
-    float buf[PF];
-    if (dirn == 0) {
-        const bool skip = lane >= 2 && e != 0 && e != e_m2;
-        float v = NEG_INF;
-        if (lane == 0) v = lp[(long)b * V];
-        else if (lane == 1 && S > 1) v = col[0];
-        out[lane] = v;
+    // per lane only 32-bit offsets: the label (its column of an lp row) and the stored column; the row bases are wave-uniform
+    bool in[NP], skip[NP];
+    unsigned e[NP], c[NP];
+    float v[NP], buf[NP][PF];
 #pragma unroll
-        for (int k = 0; k < PF; ++k) buf[k] = col[(long)min(1 + k, Tb - 1) * tstride];
-        for (int t0 = 1; t0 < Tb; t0 += PF) {
+    for (int j = 0; j < NP; ++j) {
+        const int s = lane + 64 * j;
+        e[j] = m.ext(s);
+        c[j] = m.col(s);
+        in[j] = s < S;
+        skip[j] = s >= 2 && e[j] != 0 && e[j] != (unsigned)m.ext(s - 2);
+        v[j] = (s == 0 || (s == 1 && S > 1)) ? m.lp0[e[j]] : NEG_INF;
+        m.out[c[j]] = v[j];
 #pragma unroll
-            for (int k = 0; k < PF; ++k) {
-                const int t = t0 + k;
-                if (t < Tb) {                                   // wave-uniform
-                    const float lpe = buf[k];
-                    buf[k] = col[(long)min(t + PF, Tb - 1) * tstride];
-                    float a2 = __shfl_up(v, 1, 64), a3 = __shfl_up(v, 2, 64);
-                    if (lane < 1) a2 = NEG_INF;
-                    if (!skip) a3 = NEG_INF;
-                    const float l = lse3(v, a2, a3);
-                    v = (in && l != NEG_INF) ? l + lpe : NEG_INF;
-                    out[(long)t * SP + lane] = v;
+        for (int k = 0; k < PF; ++k) buf[j][k] = (m.lp0 + min(1 + k, Tb - 1) * m.fstep)[e[j]];
+    }
+    for (int t0 = 1; t0 < Tb; t0 += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int t = t0 + k;
+            if (t < Tb) {                                        // wave-uniform
+                const float* ahead = m.lp0 + min(t + PF, Tb - 1) * m.fstep;
+                float* ot = m.out + t * m.rstep;
+                float lpe[NP], a2[NP], a3[NP];
+#pragma unroll
+                for (int j = 0; j < NP; ++j) {                   // every shuffle reads the old row, before any half is updated
+                    lpe[j] = buf[j][k];
+                    buf[j][k] = ahead[e[j]];
+                    a2[j] = __shfl_up(v[j], 1, 64);
+                    a3[j] = __shfl_up(v[j], 2, 64);
+                    if (j == 0) {
+                        if (lane < 1) a2[j] = NEG_INF;
+                    } else {
+                        const float w63 = __shfl(v[j > 0 ? j - 1 : 0], 63, 64), w62 = __shfl(v[j > 0 ? j - 1 : 0], 62, 64);
+                        if (lane == 0) { a2[j] = w63; a3[j] = w62; }
+                        if (lane == 1) a3[j] = w63;
+                    }
+                    if (!skip[j]) a3[j] = NEG_INF;
                 }
-            }
-        }
-        const float a = __shfl(v, S - 1, 64);
-        const float c = S > 1 ? __shfl(v, S - 2, 64) : NEG_INF;
-        if (lane == 0) {
-            const float m = fmaxf(a, c);
-            nll[b] = (m == NEG_INF) ? INFINITY : -(logf(expf(a - m) + expf(c - m)) + m);
-        }
-    } else {
-        const bool skip = lane + 2 < S && e != 0 && e != e_p2;
-        float v = NEG_INF;
-        if (lane == S - 1) v = lp[((long)(Tb - 1) * B + b) * V];
-        else if (lane == S - 2 && S > 1) v = col[(long)(Tb - 1) * tstride];
-        out[(long)(Tb - 1) * SP + lane] = v;
 #pragma unroll
-        for (int k = 0; k < PF; ++k) buf[k] = col[(long)max(Tb - 2 - k, 0) * tstride];
-        for (int t0 = Tb - 2; t0 >= 0; t0 -= PF) {
-#pragma unroll
-            for (int k = 0; k < PF; ++k) {
-                const int t = t0 - k;
-                if (t >= 0) {
-                    const float lpe = buf[k];
-                    buf[k] = col[(long)max(t - PF, 0) * tstride];
-                    float b2 = __shfl_down(v, 1, 64), b3 = __shfl_down(v, 2, 64);
-                    if (lane >= 63) b2 = NEG_INF;
-                    if (!skip) b3 = NEG_INF;
-                    const float l = lse3(v, b2, b3);
-                    v = (in && l != NEG_INF) ? l + lpe : NEG_INF;
-                    out[(long)t * SP + lane] = v;
+                for (int j = 0; j < NP; ++j) {
+                    const float l = lse3(v[j], a2[j], a3[j]);
+                    v[j] = (in[j] && l != NEG_INF) ? l + lpe[j] : NEG_INF;
+                    ot[c[j]] = v[j];
                 }
             }
         }
     }
-}
-
-// The same for 64 < S <= 128 (32 <= L <= 63: the long lines of BASELINE configs[3], ~1200 px with W / 30 labels): TWO extended-label
-// positions per lane (s = lane and s = lane + 64), the seam between the halves crossed with two broadcasts per step.  The generic
-// kernel took 622 us for T = 576 (1.08 us per frame, chip otherwise idle: the backward waits for it).  Same expressions in the same
-// order per element: bit-identical to ctc_alpha_beta_kernel.
-__global__ __launch_bounds__(64) void ctc_alpha_beta128_kernel(const float* __restrict__ lp, const int32_t* __restrict__ labels,
-                                                               const int32_t* __restrict__ label_offsets,
-                                                               const int32_t* __restrict__ label_lens,
-                                                               const int32_t* __restrict__ act_lens, float* __restrict__ ab,
-                                                               float* __restrict__ nll, int T, int B, int V) {
-    constexpr int SP = 128, PF = 8;
-    const int b = blockIdx.x >> 1, dirn = blockIdx.x & 1;
-    const int lane = threadIdx.x;
-    const int L = label_lens[b], S = 2 * L + 1, Tb = act_lens[b];
-    const int32_t* lab = labels + label_offsets[b];
-    float* out = ab + ((long)(b * 2 + dirn) * T) * SP;
-    if (Tb <= 0) {
-        if (dirn == 0 && lane == 0) nll[b] = (S == 1) ? 0.f : INFINITY;
-        return;
-    }
-    const int s0 = lane, s1 = lane + 64;
-    const bool in0 = s0 < S, in1 = s1 < S;
-    auto ext = [&](int s_) { return (s_ >= 0 && s_ < S && (s_ & 1)) ? lab[s_ >> 1] : 0; };
-    const int e0 = ext(s0), e1 = ext(s1);
-    const float* col0 = lp + (long)b * V + e0;             // lp[t][b][e] = col[t * B * V]
-    const float* col1 = lp + (long)b * V + e1;
-    const long tstride = (long)B * V;
-    float buf0[PF], buf1[PF];
     if (dirn == 0) {
-        const bool skip0 = s0 >= 2 && e0 != 0 && e0 != ext(s0 - 2);
-        const bool skip1 = e1 != 0 && e1 != ext(s1 - 2);
-        float v0 = NEG_INF, v1 = NEG_INF;
-        if (lane == 0) v0 = lp[(long)b * V];
-        else if (lane == 1 && S > 1) v0 = col0[0];
-        out[s0] = v0;
-        out[s1] = v1;
+        // alpha[S-1], alpha[S-2]: either may sit in any half (a short line of a batch with long ones keeps both in the first)
+        float a = NEG_INF, c = NEG_INF;
 #pragma unroll
-        for (int k = 0; k < PF; ++k) {
-            buf0[k] = col0[(long)min(1 + k, Tb - 1) * tstride];
-            buf1[k] = col1[(long)min(1 + k, Tb - 1) * tstride];
+        for (int j = 0; j < NP; ++j) {
+            const float aj = __shfl(v[j], (S - 1) & 63, 64), cj = __shfl(v[j], (S - 2) & 63, 64);
+            if ((S - 1) >> 6 == j) a = aj;
+            if (S > 1 && (S - 2) >> 6 == j) c = cj;
         }
-        for (int t0 = 1; t0 < Tb; t0 += PF) {
-#pragma unroll
-            for (int k = 0; k < PF; ++k) {
-                const int t = t0 + k;
-                if (t < Tb) {                                   // wave-uniform
-                    const float lpe0 = buf0[k], lpe1 = buf1[k];
-                    buf0[k] = col0[(long)min(t + PF, Tb - 1) * tstride];
-                    buf1[k] = col1[(long)min(t + PF, Tb - 1) * tstride];
-                    const float w63 = __shfl(v0, 63, 64), w62 = __shfl(v0, 62, 64);
-                    float a2 = __shfl_up(v0, 1, 64), a3 = __shfl_up(v0, 2, 64);
-                    float c2 = __shfl_up(v1, 1, 64), c3 = __shfl_up(v1, 2, 64);
-                    if (lane < 1) { a2 = NEG_INF; c2 = w63; }
-                    if (lane == 0) c3 = w62;
-                    if (lane == 1) c3 = w63;
-                    if (!skip0) a3 = NEG_INF;
-                    if (!skip1) c3 = NEG_INF;
-                    const float l0 = lse3(v0, a2, a3), l1 = lse3(v1, c2, c3);
-                    v0 = (in0 && l0 != NEG_INF) ? l0 + lpe0 : NEG_INF;
-                    v1 = (in1 && l1 != NEG_INF) ? l1 + lpe1 : NEG_INF;
-                    out[(long)t * SP + s0] = v0;
-                    out[(long)t * SP + s1] = v1;
-                }
-            }
-        }
-        // alpha[S-1], alpha[S-2] (a short line of a batch with long ones keeps both in the first half)
-        const float a = S - 1 >= 64 ? __shfl(v1, S - 1 - 64, 64) : __shfl(v0, S - 1, 64);
-        const float c = S < 2 ? NEG_INF : S - 2 >= 64 ? __shfl(v1, S - 2 - 64, 64) : __shfl(v0, S - 2, 64);
-        if (lane == 0) {
-            const float m = fmaxf(a, c);
-            nll[b] = (m == NEG_INF) ? INFINITY : -(logf(expf(a - m) + expf(c - m)) + m);
-        }
-    } else {
-        const bool skip0 = s0 + 2 < S && e0 != 0 && e0 != ext(s0 + 2);
-        const bool skip1 = s1 + 2 < S && e1 != 0 && e1 != ext(s1 + 2);
-        float v0 = NEG_INF, v1 = NEG_INF;
-        {
-            const float last = lp[((long)(Tb - 1) * B + b) * V];
-            if (s0 == S - 1) v0 = last;
-            else if (s0 == S - 2 && S > 1) v0 = col0[(long)(Tb - 1) * tstride];
-            if (s1 == S - 1) v1 = last;
-            else if (s1 == S - 2 && S > 1) v1 = col1[(long)(Tb - 1) * tstride];
-        }
-        out[(long)(Tb - 1) * SP + s0] = v0;
-        out[(long)(Tb - 1) * SP + s1] = v1;
-#pragma unroll
-        for (int k = 0; k < PF; ++k) {
-            buf0[k] = col0[(long)max(Tb - 2 - k, 0) * tstride];
-            buf1[k] = col1[(long)max(Tb - 2 - k, 0) * tstride];
-        }
-        for (int t0 = Tb - 2; t0 >= 0; t0 -= PF) {
-#pragma unroll
-            for (int k = 0; k < PF; ++k) {
-                const int t = t0 - k;
-                if (t >= 0) {
-                    const float lpe0 = buf0[k], lpe1 = buf1[k];
-                    buf0[k] = col0[(long)max(t - PF, 0) * tstride];
-                    buf1[k] = col1[(long)max(t - PF, 0) * tstride];
-                    const float u0 = __shfl(v1, 0, 64), u1 = __shfl(v1, 1, 64);
-                    float b2 = __shfl_down(v0, 1, 64), b3 = __shfl_down(v0, 2, 64);
-                    float d2 = __shfl_down(v1, 1, 64), d3 = __shfl_down(v1, 2, 64);
-                    if (lane == 63) { b2 = u0; b3 = u1; d2 = NEG_INF; }
-                    if (lane == 62) b3 = u0;
-                    if (!skip0) b3 = NEG_INF;
-                    if (!skip1) d3 = NEG_INF;
-                    const float l0 = lse3(v0, b2, b3), l1 = lse3(v1, d2, d3);
-                    v0 = (in0 && l0 != NEG_INF) ? l0 + lpe0 : NEG_INF;
-                    v1 = (in1 && l1 != NEG_INF) ? l1 + lpe1 : NEG_INF;
-                    out[(long)t * SP + s0] = v0;
-                    out[(long)t * SP + s1] = v1;
-                }
-            }
-        }
+        if (lane == 0) nll[b] = -lse2(a, c);                     // +inf when neither end state is reachable
     }
 }
 
@@ -497,10 +376,9 @@ extern "C" int vocr_ctc_loss_grad(const float* logits, const int32_t* labels, co
     log_softmax_rows_kernel<<<vocr_cdiv(rows, 4), 256, 0, s>>>(logits, lp, rows, v);
     VOCR_CHECK_LAUNCH("vocr_ctc_loss_grad(log_softmax)");
     const size_t smem = (size_t)(2 * (sp + 4) + sp) * sizeof(float);
-    static const int generic_only = VOCR_EXPERIMENT_INT("VOCR_CTC_GENERIC", 0);      // tests: compare the two kernels
-    if (sp == 64 && !generic_only) ctc_alpha_beta64_kernel<<<2 * b, 64, 0, s>>>(lp, labels, label_offsets, label_lens, act_lens, ab, nll, t, b, v);
-    else if (sp == 128 && !generic_only) ctc_alpha_beta128_kernel<<<2 * b, 64, 0, s>>>(lp, labels, label_offsets, label_lens, act_lens, ab, nll, t, b, v);
-    else ctc_alpha_beta_kernel<<<2 * b, 64, smem, s>>>(lp, labels, label_offsets, label_lens, act_lens, ab, nll, t, b, v, sp);
+    if (sp == 64) ctc_alpha_beta_reg_kernel<1><<<2 * b, 64, 0, s>>>(lp, labels, label_offsets, label_lens, act_lens, ab, nll, t, b, v);
+    else if (sp == 128) ctc_alpha_beta_reg_kernel<2><<<2 * b, 64, 0, s>>>(lp, labels, label_offsets, label_lens, act_lens, ab, nll, t, b, v);
+    else ctc_alpha_beta_lds_kernel<<<2 * b, 64, smem, s>>>(lp, labels, label_offsets, label_lens, act_lens, ab, nll, t, b, v, sp);
     VOCR_CHECK_LAUNCH("vocr_ctc_loss_grad(alpha_beta)");
     if (dlogits) {
         ctc_grad_kernel<<<vocr_cdiv(rows, 4), 256, (size_t)4 * v * sizeof(float), s>>>(lp, labels, label_offsets, label_lens,

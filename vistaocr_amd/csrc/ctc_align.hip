@@ -14,7 +14,7 @@
 //   kernel 2  sweep, backtrace, scores    : one wave per (line b, hypothesis q); workgroups never talk to each other.
 //
 // The sweep is a chain of lens[b] dependent steps.  Two recursions share the lattice: max (Viterbi) with a back pointer per (t, s),
-// and logsumexp (the forward score, same expression as ctc_alpha_beta_kernel's lse3).
+// and logsumexp (the forward score, the lse3 of ctc_math.h, as in the alpha/beta sweeps of ctc.hip).
 // TIE RULE of the Viterbi recursion: among equal predecessors prefer s, then s-1, then s-2 (a predecessor replaces the current
 // choice only when STRICTLY greater); at the last frame the final blank 2L wins over 2L-1 on equality.
 //   S <= 64 : one extended position per lane, both previous rows in registers, neighbours by wave shuffles, the frame's gathered
@@ -72,16 +72,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
     const long tstride = (long)B * V;
     const float* lpb = clp + (long)b * V;                       // lpb[t * tstride + v]
 
-    // a labelling that cannot be aligned: bad length, a label outside (0, V) or in the blank's class
-    bool bad = L < 0 || L > max_label_len;
-    if (!bad) {
-        bool mine = false;
-        for (int p = lane; p < L; p += 64) {
-            const int v = lab[p];
-            mine |= (v <= 0 || v >= V) || class_of(canon, min(max(v, 0), V - 1)) == 0;
-        }
-        bad = __any(mine);
-    }
+    const bool bad = labelling_bad(canon, lab, L, V, max_label_len, lane);          // it cannot be aligned
     const int S = 2 * L + 1;
     float vit = NEG_INF, fwd = NEG_INF;
     int s_end = 0;
@@ -132,8 +123,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
         const float as = __shfl(vs, S - 1, 64), cs = S > 1 ? __shfl(vs, S - 2, 64) : NEG_INF;
         s_end = cm > am ? S - 2 : S - 1;
         vit = fmaxf(am, cm);
-        const float m = fmaxf(as, cs);
-        fwd = (m == NEG_INF) ? NEG_INF : logf(expf(as - m) + expf(cs - m)) + m;
+        fwd = lse2(as, cs);
     } else {
         // rows with 2 leading -inf pads: rm[2 + s], rs[2 + s]; ext[s] = label | class << 16; em[k][s] the staged log-probabilities
         float* rows = ROWS_GLOBAL ? rows_ws + (long)prob * rows_floats : sm;
@@ -191,8 +181,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
         const float as = rs[2 + S - 1], cs = rs[2 + S - 2];
         s_end = cm > am ? S - 2 : S - 1;
         vit = fmaxf(am, cm);
-        const float m = fmaxf(as, cs);
-        fwd = (m == NEG_INF) ? NEG_INF : logf(expf(as - m) + expf(cs - m)) + m;
+        fwd = lse2(as, cs);
     }
 
     if (vit == NEG_INF) fwd = NEG_INF;                          // no path: both scores -inf

@@ -1,19 +1,12 @@
 // What the CTC alignment (ctc_align.hip) and the CTC edit scores (ctc_edit.hip) share: the class rule of the beam searches and the
 // class log-probability pass, so that both read the same bits for a (frame, column).
 #pragma once
-#include "vocr_common.h"
+#include "ctc_math.h"
 
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
 constexpr int VMAX = 256;                    // as vocr_ctc_beam_search
 constexpr int NMAX = 128;
-
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-    float m = fmaxf(a, fmaxf(b, c));
-    if (m == NEG_INF) return NEG_INF;
-    return logf(expf(a - m) + expf(b - m) + expf(c - m)) + m;
-}
 
 // canon sanitised as in the beam searches: an entry that is not a canonical index <= v stands for itself
 __device__ __forceinline__ int class_of(const int32_t* __restrict__ canon, int v) {
@@ -21,6 +14,18 @@ __device__ __forceinline__ int class_of(const int32_t* __restrict__ canon, int v
     int c = canon[v];
     if (c < 0 || c > v || canon[c] != c) c = v;
     return c;
+}
+
+// a labelling that cannot be scored: bad length, a label outside (0, V) or in the blank's class.  Wave-uniform.
+__device__ __forceinline__ bool labelling_bad(const int32_t* __restrict__ canon, const int32_t* __restrict__ lab, int L, int V,
+                                              int max_label_len, int lane) {
+    if (L < 0 || L > max_label_len) return true;
+    bool mine = false;
+    for (int p = lane; p < L; p += 64) {
+        const int v = lab[p];
+        mine |= (v <= 0 || v >= V) || class_of(canon, min(max(v, 0), V - 1)) == 0;
+    }
+    return __any(mine);
 }
 
 // 16 rows per block, one wave per row at a time.  clp[row][v] = ln P(class of v | frame); rows with t >= lens[b] are never read and not

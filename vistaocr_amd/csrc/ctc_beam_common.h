@@ -5,20 +5,13 @@
 // (score desc, slot id asc), the final ranking and the backtrack of the n-best from the node pool.  Only integer LDS atomics;
 // every float is computed by a fixed thread in a fixed order.
 #pragma once
-#include "vocr_common.h"
+#include "ctc_math.h"
 
 namespace ctcbeam {
 
 constexpr int BT = 256;            // threads per line
 constexpr int KMAX = 128;
 constexpr int VMAX = 256;
-constexpr float NEG_INF = -INFINITY;
-
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == NEG_INF) return NEG_INF;
-    return m + logf(expf(a - m) + expf(b - m));
-}
 
 // order-preserving map of a non-NaN float to uint32 (larger score -> larger key)
 __device__ __forceinline__ unsigned score_key(float s) {

@@ -40,24 +40,6 @@ constexpr int TB = 8;                        // kernel 2, S > 64: frames staged 
 constexpr size_t LDS_BUDGET = 144 * 1024;    // of the 160 KiB per CU
 constexpr size_t LATTICE_BYTES_MAX = (size_t)1 << 31;
 
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == NEG_INF) return NEG_INF;
-    return logf(expf(a - m) + expf(b - m)) + m;
-}
-
-// a labelling no edit of which is scored: bad length, a label outside (0, V) or in the blank's class.  Wave-uniform.
-__device__ __forceinline__ bool labelling_bad(const int32_t* __restrict__ canon, const int32_t* __restrict__ lab, int L, int V,
-                                              int max_label_len, int lane) {
-    if (L < 0 || L > max_label_len) return true;
-    bool mine = false;
-    for (int p = lane; p < L; p += 64) {
-        const int v = lab[p];
-        mine |= (v <= 0 || v >= V) || class_of(canon, min(max(v, 0), V - 1)) == 0;
-    }
-    return __any(mine);
-}
-
 // grid.x = B * n * 2 (direction fastest), 64 threads.  lat: [B * n][2][SM = 2 * max_label_len + 1][T] floats.  Dynamic LDS (S > 64 only):
 // the row with 2 leading -inf pads, ext[SP], the staged log-probabilities [TB][SP].
 __global__ __launch_bounds__(64) void ctc_edit_lattice_kernel(const float* __restrict__ clp, const int32_t* __restrict__ lens,
@@ -167,18 +149,6 @@ __global__ __launch_bounds__(64) void ctc_edit_lattice_kernel(const float* __res
 #undef POS
     if (dir == 0 && lane == 0) out_ctc[prob] = lse2(as, cs);
 }
-
-// a logsumexp kept as (max, sum): one exponential per term
-struct LseAcc {
-    float m = NEG_INF, s = 0.f;
-    __device__ __forceinline__ void add(float v) {
-        if (v == NEG_INF) return;
-        const float e = expf(-fabsf(m - v));                     // m = -inf: 0
-        s = v > m ? s * e + 1.f : s + e;
-        m = fmaxf(m, v);
-    }
-    __device__ __forceinline__ float get() const { return m == NEG_INF ? NEG_INF : m + logf(s); }
-};
 
 // what kernel 3 needs of one frame t: the column's and the blank's class log-probability, alpha[t][2p], alpha[t][2p-1] and
 // beta[t+1][2p+1 .. 2p+3] (-inf where the position does not exist)

@@ -40,18 +40,6 @@ constexpr int ANCHOR_START = 1, ANCHOR_END = 2;
 constexpr int TRIM_START = 4, TRIM_END = 8;     // the span leaves out the first / last label (whole-word search pads with spaces)
 constexpr int NLAYOUT = 4;                   // S <= 16, <= 32, <= 64, <= 256
 
-// a logsumexp kept as (max, sum): one exponential per term
-struct LseAcc {
-    float m = NEG_INF, s = 0.f;
-    __device__ __forceinline__ void add(float v) {
-        if (v == NEG_INF) return;
-        const float e = expf(-fabsf(m - v));                     // m = -inf: 0
-        s = v > m ? s * e + 1.f : s + e;
-        m = fmaxf(m, v);
-    }
-    __device__ __forceinline__ float get() const { return m == NEG_INF ? NEG_INF : m + logf(s); }
-};
-
 // 16 rows per block, one wave per row at a time.  notc[row][v] = ln(1 - P(class of v | frame)) from the raw logits; rows with
 // t >= lens[b] are never read and not written.  A row of -inf gives -inf.
 __global__ __launch_bounds__(256) void not_class_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens,
@@ -239,12 +227,6 @@ __global__ __launch_bounds__(256) void keyword_plan_kernel(const int32_t* __rest
             if (k == j) o = off[j]++;
         perm[o] = q | ((kk & 4) ? (int)0x80000000 : 0);
     }
-}
-
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == NEG_INF) return NEG_INF;
-    return logf(expf(a - m) + expf(b - m)) + m;
 }
 
 // one cell of both recursions: the expected-count value a and the best path's (score m, start frame ms) from the cell itself, its
