@@ -541,6 +541,35 @@ int vocr_ctc_edit_scores(const float* logits, const int32_t* lens, int t, int b,
                          float* out_ctc, float* out_sub, float* out_del, float* out_ins,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Weighted n-best CTC scores and gradient: what minimum-error-rate training over a beam search's n-best list is made of ---- */
+/* For n labellings of each line: out_ctc[B][n] = ln P_ctc(labels[b][q] | x_b), and with weights[B][n] (device fp32) given,
+ *   dlogits[T][B][V] = d/dlogits  sum_b sum_q weights[b][q] * ln P_ctc(labels[b][q] | x_b)
+ * in one tensor, the sum over the SCORABLE hypotheses (finite out_ctc).  Inputs, classes, blank, transition rule, the (line b,
+ * hypothesis q) layout and the validity rules are vocr_ctc_align's and vocr_ctc_edit_scores's: logits raw (log-softmax inside), lens
+ * clamped to [0, T], canon NULL = identity, a label given as any member index stands for its class.  out_ctc is vocr_ctc_align's
+ * second score and holds the same bits as vocr_ctc_edit_scores's out_ctc (the same kernel computes it), -inf in the same places: a
+ * labelling that does not fit the frames or uses a class the frames give -inf, a label <= 0 or >= v or in the blank's class,
+ * label_lens outside [0, max_label_len], lens[b] = 0 with L > 0 (L = 0 then scores 0).
+ * With p_t(v) the softmax of frame t, P_t(c) the sum of p_t over the columns of class c and occ_q(t, c) the posterior probability,
+ * given labelling q, that frame t is spent in class c (the sum over the extended positions s of class c of
+ * alpha_t(s) * beta_t(s) / (P_t(c) * P_q); it sums to 1 over c):
+ *   dlogits[t][b][v] = p_t(v) * ( sum_q w_q * occ_q(t, class(v)) / P_t(class(v))  -  sum_q w_q ).
+ * Rows t >= lens[b] are written as zeros.  A hypothesis with a -inf score contributes exactly nothing, whatever its weight; a
+ * duplicate labelling counts twice.  -inf logits are legal: a column with p_t(v) = 0 gets 0, and a class with P_t(c) = 0 never yields
+ * NaN or inf.  No floating-point atomics: every sum has a fixed order, results are bit-identical from run to run, and a line's rows
+ * depend on that line alone.  weights == NULL (then dlogits must be NULL, and the other way round): scores only - the forward sweep
+ * alone, no lattice stored; out_ctc holds the same bits as in a call with weights.
+ * Limits: 2 <= v <= 256, 1 <= n <= 128, 0 <= max_label_len <= t, label_stride >= max_label_len, t * b * n < 2^31, max_label_len <=
+ * 1823 (one row of the sweep in the LDS), and the forward and backward lattices of all labellings,
+ * b * n * 8 * t * (2 * max_label_len + 1) bytes, at most 2 GiB.  Workspace from vocr_ctc_nbest_workspace_bytes (0 for an unsupported
+ * shape) = the class log-probabilities (t * b * v * 4 bytes rounded up to 16) + the lattices; a scores-only call uses, and checks
+ * for, the class log-probabilities alone.  Bad arguments and unsupported shapes fail with VOCR_EINVAL before any launch. */
+size_t vocr_ctc_nbest_workspace_bytes(int t, int b, int v, int n, int max_label_len);
+int vocr_ctc_nbest_grad(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                        const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
+                        const float* weights, float* out_ctc, float* dlogits,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC keyword search: "does this line contain the word X" without decoding (the lattice use of eesen's decode, lattice-free) ---- */
 /* For every (line b, query q) the EXPECTED NUMBER of occurrences of the query as a contiguous substring of the collapsed labelling,
  * E = sum over all frame paths pi of P(pi | x) * #occurrences(query in B(pi)): exact under the CTC model, a sum over all v^len paths

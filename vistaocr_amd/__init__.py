@@ -14,12 +14,13 @@ from .align import CtcAligner                                                   
 from .keyword import KeywordHits, KeywordSpotter                                        # noqa: F401,E402
 from .score import ErrorScorer, ErrorStats, OracleStats                                  # noqa: F401,E402
 from .ctc import CTCLoss                                                                # noqa: F401,E402
+from .risk import MinErrorRateLoss                                                      # noqa: F401,E402
 from .decoder import ArgmaxDecoder, BeamDecoder, WordBeamDecoder                        # noqa: F401,E402
 from .lm import CharNgramLM, WordNgramLM                                                # noqa: F401,E402
 from .model import CnnOcrModel                                                          # noqa: F401,E402
 from .train import FlatClampAdam, make_optimizer, seed_rank, train, train_async                                    # noqa: F401,E402
 from .dataset import OcrDataset                                                         # noqa: F401,E402
 
-__all__ = ["Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "ArgmaxDecoder", "BeamDecoder",
+__all__ = ["Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "ArgmaxDecoder", "BeamDecoder",
            "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "ErrorScorer", "ErrorStats", "OracleStats",
            "CnnOcrModel", "FlatClampAdam", "make_optimizer", "seed_rank", "train", "train_async", "OcrDataset"]

@@ -117,6 +117,8 @@ SIGNATURES = {
     "vocr_ctc_align": (I, [P, P, I, I, I, P, P, P, I, I, I, P, P, P, P, Z, P]),
     "vocr_ctc_edit_workspace_bytes": (Z, [I, I, I, I, I]),
     "vocr_ctc_edit_scores": (I, [P, P, I, I, I, P, P, P, I, I, I, P, P, P, P, P, Z, P]),
+    "vocr_ctc_nbest_workspace_bytes": (Z, [I, I, I, I, I]),
+    "vocr_ctc_nbest_grad": (I, [P, P, I, I, I, P, P, P, I, I, I, P, P, P, P, Z, P]),
     "vocr_ctc_keyword_workspace_bytes": (Z, [I, I, I, I, I]),
     "vocr_ctc_keyword_scores": (I, [P, P, I, I, I, P, P, P, P, I, I, I, P, P, P, P, Z, P]),
     "vocr_edit_stats_workspace_bytes": (Z, [I, I, I, I, I, I, I]),

@@ -1456,6 +1456,35 @@ def ctc_edit_scores(logits, lens, labels, label_lens, canon=None):
     return ctc, sub, dele, ins
 
 
+def ctc_nbest(logits, lens, labels, label_lens, canon=None, weights=None):
+    """Weighted n-best CTC scores and gradient (vocr_ctc_nbest_grad).  Arguments as for ctc_align; `weights` None or an fp32 device
+    tensor shaped like `label_lens`.  Returns, on the device, (ctc fp32 [B,n] (or [B] for 2-d labels) = ln P_ctc(labels | x), -inf for a
+    labelling without a score; dlogits), dlogits None without weights, else fp32 [T,B,V] = the gradient with respect to the raw logits
+    of sum_b sum_q weights[b][q] * ctc[b][q] over the hypotheses with a finite score (rows past `lens` are zero).  Without weights only
+    the forward sweeps run and only the class log-probabilities are allocated."""
+    logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze = _labelling_args(
+        "ctc_nbest", "vocr_ctc_nbest_workspace_bytes",
+        "2 <= V <= 256, n <= 128, label length <= 1823, B * n * 8 * T * (2 * label length + 1) bytes of lattices <= 2 GiB",
+        logits, lens, labels, label_lens, canon)
+    T, B, V = logits.shape
+    dev = logits.device
+    dlogits = None
+    if weights is None:
+        nbytes = (T * B * V * 4 + 15) // 16 * 16           # a scores-only call stores no lattice
+    else:
+        _need_gpu(weights)
+        if weights.dtype != torch.float32 or weights.numel() != B * n:
+            raise RuntimeError("ctc_nbest: weights must be fp32 with one entry per hypothesis (weights %s, label_lens %s)"
+                               % (tuple(weights.shape), tuple(label_lens.shape)))
+        weights = weights.detach().contiguous()
+        dlogits = torch.empty_like(logits)
+    ctc = torch.empty(B, n, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    call("vocr_ctc_nbest_grad", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(labels), _p(label_lens), n, stride, M, _p(weights), _p(ctc),
+         _p(dlogits), _p(ws), ws.numel() * 4, _stream())
+    return (ctc[:, 0] if squeeze else ctc), dlogits
+
+
 def ctc_keyword_scores(logits, lens, queries, query_lens, query_flags=None, canon=None):
     """CTC keyword search (vocr_ctc_keyword_scores) on raw logits [T,B,V]: for every (line, query) the natural log of the EXPECTED
     NUMBER of occurrences of the query as a contiguous substring of the collapsed labelling - exact, over all frame paths; min(1, count)
