@@ -1,19 +1,32 @@
-"""A change to the alpha/beta sweeps of ctc.hip that must move neither bits nor time: vocr_ctc_loss_grad of the in-tree libvocr.so
-against the PARENT commit's library at scripts/_cut/libvocr.so (build a clean checkout of the parent outside the tree and copy its
-libvocr.so there), both loaded with ctypes into one process.
+"""A change to the CTC kernels that must move neither bits nor time: the in-tree libvocr.so against the PARENT commit's library at
+scripts/_cut/libvocr.so (build a clean checkout of the parent outside the tree and copy its libvocr.so there), both loaded with ctypes
+into one process.  --what chooses the entry points:
 
-Bits: every (case, regime) of tests.ctc_ref.all_cases() at each max_label_len of tests/test_ctc_fp64_gpu.py's forced() (every launch
-path that admits the batch), the workspace filled with a constant first; SHA-256 of nll, of dlogits and of the WHOLE workspace (the
-log-softmax, every alpha / beta row and pad column, the rows past act_len that no kernel may write) under both libraries.  Every digest
-pair must be equal; the script exits 1 otherwise.
+loss (the alpha/beta sweeps of ctc.hip): vocr_ctc_loss_grad.
+  Bits: every (case, regime) of tests.ctc_ref.all_cases() at each max_label_len of tests/test_ctc_fp64_gpu.py's forced() (every launch
+  path that admits the batch); SHA-256 of nll, of dlogits and of the WHOLE workspace (the log-softmax, every alpha / beta row and pad
+  column, the rows past act_len that no kernel may write).
+  Time: bench_full (T 294, B 32, V 96: one position per lane), c4_ragged (T 588, B 32, V 166: two per lane), generic_long (T 1200, B 2,
+  V 166: the LDS path).
 
-Time: the whole call with HIP events on the workloads' own shapes - bench_full (T 294, B 32, V 96: one position per lane), c4_ragged
-(T 588, B 32, V 166: two per lane), generic_long (T 1200, B 2, V 166: the LDS path) - both libraries warmed up on every shape, then
-windows of --window calls alternating between the libraries for --rounds rounds.  Per shape and library: the median of the round
-medians, and the parent's own max - min over its rounds, which is the only margin: the new median must not exceed the parent's median
-plus that spread.
+labelling (the sweep, the host preamble and the class rule the scorers of a known labelling share): the entries of ENTRIES below.  A
+  call is RECORDED where vistaocr_amd.ops makes it - the C arguments and the tensors behind their pointers - and replayed on both
+  libraries, so the inputs are the tests' own.
+  Bits: vocr_ctc_align, vocr_ctc_edit_scores and vocr_ctc_nbest_grad (with and without weights) on every case of tests/nbest_cases.py,
+  the small exact cases of tests/test_align_cpu.py and tests/test_edit_cpu.py (what the GPU tests of both run), the empty and invalid
+  labellings of their edge cases, and two lines of 4000 frames with 1796 and 1554 labels (beyond 1663 the alignment keeps its rows in
+  the workspace); vocr_ctc_keyword_scores on every call the tests of tests/test_kws_gpu.py make; vocr_ctc_beam_search and
+  vocr_ctc_word_beam_search on one English-canon case each of tests/beam_cases.py.  SHA-256 of every output and of the whole workspace.
+  Time: T 294, B 32, V 96 (scripts/align_bench.py, edit_bench.py, risk_bench.py), the n = 4 and n = 16 best of a K = 16 search on peaky
+  logits at p_char 0.35 (43 - 67 labels: the rows in LDS) and 0.10 (5 - 24 labels: one position per lane), packed to the longest.
 
-    python scripts/ctc_parent_ab.py [--window 200] [--rounds 5] [--out profiles/ctc_mirror_ab.txt]"""
+Bits, both: outputs and workspace are filled with a constant before the call, so bytes that no kernel writes compare equal trivially;
+every digest pair must be equal, and the script exits 1 otherwise.
+Time, both: the whole call with HIP events, both libraries warmed up on every shape, then windows of --window calls alternating between
+the libraries for --rounds rounds.  Per shape and library: the median of the round medians, and the parent's own max - min over its
+rounds, which is the only margin: the new median must not exceed the parent's median plus that spread.
+
+    python scripts/ctc_parent_ab.py [--what loss|labelling] [--window 200] [--rounds 5] [--out profiles/ctc_<what>_ab.txt]"""
 import argparse
 import ctypes
 import functools
@@ -35,9 +48,21 @@ FILL = -3.0
 TIMED = ("bench_full", "c4_ragged", "generic_long")
 
 
+# labelling: C entry -> (its workspace-size function, where that function's arguments sit in the entry's argument list, the output
+# pointers, the workspace pointer; the workspace's size follows it)
+ENTRIES = {
+    "vocr_ctc_align": ("vocr_ctc_align_workspace_bytes", (2, 3, 4, 8, 10), (11, 12, 13), 14),
+    "vocr_ctc_edit_scores": ("vocr_ctc_edit_workspace_bytes", (2, 3, 4, 8, 10), (11, 12, 13, 14), 15),
+    "vocr_ctc_nbest_grad": ("vocr_ctc_nbest_workspace_bytes", (2, 3, 4, 8, 10), (12, 13), 14),
+    "vocr_ctc_keyword_scores": ("vocr_ctc_keyword_workspace_bytes", (2, 3, 4, 9, 11), (12, 13, 14), 15),
+    "vocr_ctc_beam_search": ("vocr_ctc_beam_workspace_bytes", (2, 3, 4, 6, 7), (16, 17, 18), 19),
+    "vocr_ctc_word_beam_search": ("vocr_ctc_word_beam_workspace_bytes", (2, 3, 4, 6, 7), (29, 30, 31), 32),
+}
+
+
 def open_lib(path):
     lib = ctypes.CDLL(path)
-    for name in ("vocr_ctc_workspace_bytes", "vocr_ctc_loss_grad", "vocr_last_error"):
+    for name in ["vocr_ctc_workspace_bytes", "vocr_ctc_loss_grad", "vocr_last_error"] + list(ENTRIES) + [e[0] for e in ENTRIES.values()]:
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _lib.SIGNATURES[name]
     return lib
@@ -93,25 +118,197 @@ def window(call, lib, n):
     return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e3          # us
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--window", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--parent", default=os.path.join(ROOT, "scripts", "_cut", "libvocr.so"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ctc_mirror_ab.txt"))
-    args = ap.parse_args()
-    assert args.window >= 200 and args.rounds >= 5
-    new, parent = open_lib(_lib.LIB_PATH), open_lib(args.parent)
-    libs = (new, parent)
-    lines = []
+def race(call, libs, window_calls, rounds):
+    """call.run(lib) timed in alternating windows; returns (new median, parent median, parent spread, new rounds, parent rounds)"""
+    med = {0: [], 1: []}
+    for r in range(rounds):
+        for i in ((0, 1) if r % 2 == 0 else (1, 0)):
+            med[i].append(window(call, libs[i], window_calls))
+    return float(np.median(med[0])), float(np.median(med[1])), max(med[1]) - min(med[1]), med[0], med[1]
 
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
 
-    say("device: %s" % torch.cuda.get_device_name(0))
-    say("new: %s   parent: %s" % (os.path.relpath(_lib.LIB_PATH, ROOT), os.path.relpath(args.parent, ROOT)))
+class Replay:
+    """one recorded call of an ENTRIES entry: its C arguments, the tensors behind its output and workspace pointers"""
+
+    def __init__(self, name, args, tensors):
+        _, _, outs, ws = ENTRIES[name]
+        self.name, self.args = name, args
+        self.outs = [tensors[args[i]] for i in outs if args[i] is not None]
+        self.ws = tensors[args[ws]]
+        self.keep = tensors                                   # the inputs stay alive with the call
+
+    def run(self, lib):
+        rc = getattr(lib, self.name)(*self.args)
+        if rc != 0:
+            raise RuntimeError("%s failed (%d): %s" % (self.name, rc, (lib.vocr_last_error() or b"?").decode()))
+
+    def sizes(self, lib):
+        fn, where, _, _ = ENTRIES[self.name]
+        return getattr(lib, fn)(*[self.args[i] for i in where])
+
+    def digests(self, lib):
+        for t in self.outs + [self.ws]:
+            t.fill_(FILL)
+        self.run(lib)
+        torch.cuda.synchronize()
+        return [hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest() for t in self.outs + [self.ws]]
+
+
+class Recorder:
+    """while active, every call of an ENTRIES entry that vistaocr_amd.ops makes and that succeeds is kept as a Replay"""
+
+    def __enter__(self):
+        from vistaocr_amd import ops
+        self.calls, self.tensors, self.ops, self.p, self.call = [], {}, ops, ops._p, ops.call
+
+        def p(t):
+            if t is not None:
+                self.tensors[t.data_ptr()] = t
+            return self.p(t)
+
+        def call(name, *args):
+            self.call(name, *args)
+            if name in ENTRIES:
+                self.calls.append(Replay(name, args, dict(self.tensors)))
+
+        ops._p, ops.call = p, call
+        return self
+
+    def __exit__(self, *exc):
+        self.ops._p, self.ops.call = self.p, self.call
+        self.tensors = {}
+
+
+def record(fn, *a, **k):
+    with Recorder() as rec:
+        fn(*a, **k)
+    return rec.calls
+
+
+def labelling_calls(x, lens, labels, label_lens, canon, w):
+    """the four calls on one batch of device tensors: alignment, edit scores, n-best with and without weights"""
+    from vistaocr_amd import ops
+
+    def go():
+        ops.ctc_align(x, lens, labels, label_lens, canon)
+        ops.ctc_edit_scores(x, lens, labels, label_lens, canon)
+        ops.ctc_nbest(x, lens, labels, label_lens, canon, w)
+        ops.ctc_nbest(x, lens, labels, label_lens, canon)
+    calls = record(go)
+    assert [c.name for c in calls] == ["vocr_ctc_align", "vocr_ctc_edit_scores", "vocr_ctc_nbest_grad", "vocr_ctc_nbest_grad"]
+    return list(zip(("align", "edit", "nbest+w", "nbest"), calls))
+
+
+def host_batch(x, lens, hyps, canon, width=None):
+    """numpy logits [T,B,V] and hyps[b][q] (lists or None) as the device tensors of labelling_calls"""
+    from tests import nbest_ref as nr
+    M = max([len(h) for row in hyps for h in row if h is not None] + [1]) if width is None else width
+    n = max(len(row) for row in hyps)
+    labels, label_lens = nr.pack([list(row) + [None] * (n - len(row)) for row in hyps], M, "cuda")
+    B = len(hyps)
+    w = torch.linspace(-1.0, 1.0, B * n, device="cuda").reshape(B, n).contiguous()
+    cd = None if canon is None else torch.as_tensor(np.asarray(canon), dtype=torch.int32).cuda()
+    return (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda(), torch.tensor([int(v) for v in lens], dtype=torch.int32).cuda(),
+            labels, label_lens, cd, w)
+
+
+def labelling_bit_cases():
+    """(case name, [(entry label, Replay)])"""
+    from tests import align_ref as ar
+    from tests import beam_cases as bc
+    from tests import beam_data as bd
+    from tests import nbest_cases as nc
+    from tests import test_align_cpu as tac
+    from tests import test_beam_fp64_gpu as tb
+    from tests import test_edit_cpu as tec
+    from tests import test_kws_gpu as tk
+    from tests import test_nbest_gpu as tn
+    from tests import test_word_beam_fp64_gpu as tw
+    for c in nc.CASES:
+        yield "nbest_cases " + c[0], labelling_calls(*tn._device_case(nc.build_case(c[0])))
+    for i, (T, V, labels, canon) in enumerate(tac.EXACT):
+        yield "align exact %d" % i, labelling_calls(*host_batch(tac.exact_logits(i, T, V)[:, None, :], [T], [[labels]], canon))
+    for i, (T, V, length, labels, canon, _) in enumerate(tec.CASES):
+        yield "edit exact %d" % i, labelling_calls(*host_batch(tec.case_logits(i)[:, None, :], [length], [[labels]], canon))
+    x = np.random.default_rng(21).normal(0, 1, (40, 7, 96)).astype(np.float32)       # test_edge_cases / test_edge_shapes
+    g = [ar.greedy_labels(x[:, b], 40) for b in range(7)]
+    yield "empty and invalid", labelling_calls(*host_batch(x, [0, 0, 40, 3, 40, 40, 40],
+                                                           [[[]], [g[1][:3]], [[]], [g[3][:9]], [[5, 96, 7]], [[5, 0, 7]], [[-3]]], None))
+    yield "ragged, 6 labels", labelling_calls(*host_batch(x, [0, 1, 40, 17, 2, 39, 33], [[g[b][:6]] for b in range(7)], None))
+    x = bd.peaky_logits(np.random.default_rng(31), 4000, 2, 96, p_char=0.9)           # test_long_lines_keep_rows_and_back_pointers_in_the_workspace
+    hyps = [[ar.greedy_labels(x[:, b], ln)] for b, ln in enumerate((4000, 3500))]
+    assert len(hyps[0][0]) > 1663 > len(hyps[1][0]) > 1000
+    yield "T 4000, %d and %d labels" % (len(hyps[0][0]), len(hyps[1][0])), labelling_calls(*host_batch(x, [4000, 3500], hyps, None))
+    kws = [(tk.test_query_lengths_and_lane_layouts, (L,)) for L in tk.QUERY_LENGTHS]
+    kws += [(f, ()) for f in (tk.test_mixed_lengths_land_at_the_callers_index, tk.test_frame_counts,
+                              tk.test_alphabet_sizes_classes_and_minus_infinity, tk.test_peak_before_the_start_and_after_the_end,
+                              tk.test_tie_rule, tk.test_anchors_and_the_forward_score, tk.test_trimmed_spans,
+                              tk.test_invalid_queries_poison_only_their_own_column)]
+    for fn, a in kws:
+        calls = [c for c in record(fn, *a) if c.name == "vocr_ctc_keyword_scores"]
+        yield "kws %s%s" % (fn.__name__[5:29], a if a else ""), [("keyword %d" % i, c) for i, c in enumerate(calls)]
+    case = bc.char_case("K16_lm")
+    yield "beam_cases K16_lm", [("beam", record(tb._run, case.x, case.lens, case.K, case.nbest, canon=case.canon, lm=case.lm, alpha=case.alpha,
+                                                beta=case.beta, prune=case.prune)[0])]
+    case = bc.word_case("w_K16_oov")
+    yield "beam_cases w_K16_oov", [("word beam", record(tw._run, case.x, case.lens, case.K, case.nbest, case.lm, canon=case.canon,
+                                                        alpha=case.alpha, beta=case.beta, oov=case.oov)[0])]
+
+
+def labelling_timed_cases():
+    """(shape name, longest labelling, [(entry label, Replay)]): the n best of a K = 16 search over the English classes"""
+    import vistaocr_amd as va
+    from tests import beam_data as bd
+    from vistaocr_amd import ops
+    T, B, V = 294, 32, 96
+    canon = np.array(va.english_alphabet().canonical_indices())
+    cls = np.nonzero(canon == np.arange(V))[0][1:]
+    cd = torch.as_tensor(canon, dtype=torch.int32).cuda()
+    for p_char in (0.35, 0.10):
+        xd = torch.from_numpy(bd.peaky_logits(np.random.default_rng(7), T, B, V, classes=cls, p_char=p_char)).cuda()
+        lens = torch.full((B,), T, dtype=torch.int32, device="cuda")
+        for n in (4, 16):
+            lab, ln, _ = ops.ctc_beam_search(xd, [T] * B, cd, 16, n)
+            M = max(int(ln.max()), 1)
+            w = torch.linspace(-1.0, 1.0, B * n, device="cuda").reshape(B, n).contiguous()
+            yield "p_char %.2f n %2d" % (p_char, n), M, labelling_calls(xd, lens, lab[:, :, :M].contiguous(), ln.contiguous(), cd, w)
+
+
+def labelling_tables(libs, args, say):
+    new, parent = libs
+    say("bits: SHA-256 (first 12 hex digits) of every output and of the whole workspace, all filled with %g before the call" % FILL)
+    fmt = "%-42s %-11s | %-64s | %s"
+    say(fmt % ("case", "entry", "outputs in the C order, workspace", "new vs parent"))
+    differ = pairs = 0
+    for case, calls in labelling_bit_cases():
+        for label, call in calls:
+            assert call.sizes(new) == call.sizes(parent) > 0, "the two libraries size the workspace differently: %s %s" % (case, label)
+            dn, dp = call.digests(new), call.digests(parent)
+            bad = sum(a != b for a, b in zip(dn, dp))
+            differ, pairs = differ + bad, pairs + len(dn)
+            say(fmt % (case, label, " ".join(d[:12] for d in dn), "equal" if not bad else "DIFFER (parent %s)" % " ".join(d[:12] for d in dp)))
+    say("digest pairs: %d, of which differ: %d" % (pairs, differ))
     say("")
+    say("time: the whole call (class log-probabilities and every kernel behind them), HIP events, us; per round the median of a window of "
+        "%d calls, the libraries alternating, %d rounds after a warm-up window of each" % (args.window, args.rounds))
+    tfmt = "%-16s %3s %-8s | %9s %9s %9s | %9s | %s"
+    say(tfmt % ("shape", "M", "entry", "parent", "p. spread", "new", "new - p.", "new <= parent + spread"))
+    slower = 0
+    for shape, M, calls in labelling_timed_cases():
+        for label, call in calls:
+            for lib in libs:
+                window(call, lib, args.window)
+            mn, mp, spread, rn, rp = race(call, libs, args.window, args.rounds)
+            ok = mn <= mp + spread
+            slower += not ok
+            say(tfmt % (shape, M, label, "%.2f" % mp, "%.2f" % spread, "%.2f" % mn, "%+.2f" % (mn - mp), "yes" if ok else "NO"))
+            say("    rounds, parent: %s   new: %s" % (" ".join("%.2f" % v for v in rp), " ".join("%.2f" % v for v in rn)))
+    say("shapes slower than the parent's median plus its spread: %d" % slower)
+    return differ, slower
+
+
+def loss_tables(libs, args, say):
+    new, parent = libs
     say("bits: SHA-256 (first 12 hex digits) of nll, dlogits and the whole workspace, filled with %g before the call" % FILL)
     fmt = "%-17s %-12s %4s %-7s | %-12s %-12s %-12s | %s"
     say(fmt % ("case", "regime", "mll", "path", "nll", "dlogits", "workspace", "new vs parent"))
@@ -137,19 +334,39 @@ def main():
         for lib in libs:
             window(call, lib, args.window)
     for name, (call, lmax) in zip(TIMED, calls):
-        med = {0: [], 1: []}
-        for r in range(args.rounds):
-            for i in ((0, 1) if r % 2 == 0 else (1, 0)):
-                med[i].append(window(call, libs[i], args.window))
-        mn, mp = float(np.median(med[0])), float(np.median(med[1]))
-        spread = max(med[1]) - min(med[1])
+        mn, mp, spread, rn, rp = race(call, libs, args.window, args.rounds)
         ok = mn <= mp + spread
         slower += not ok
         say(tfmt % (name, kernel_of(lmax), *call.shape, "%.2f" % mp, "%.2f" % spread, "%.2f" % mn, "%+.2f" % (mn - mp),
                     "yes" if ok else "NO"))
-        say("    rounds, parent: %s   new: %s" % (" ".join("%.2f" % v for v in med[1]), " ".join("%.2f" % v for v in med[0])))
+        say("    rounds, parent: %s   new: %s" % (" ".join("%.2f" % v for v in rp), " ".join("%.2f" % v for v in rn)))
     say("shapes slower than the parent's median plus its spread: %d" % slower)
-    with open(args.out, "w") as fh:
+    return differ, slower
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--parent", default=os.path.join(ROOT, "scripts", "_cut", "libvocr.so"))
+    ap.add_argument("--what", choices=("loss", "labelling"), default="loss")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    out = args.out or os.path.join(ROOT, "profiles", "ctc_mirror_ab.txt" if args.what == "loss" else "ctc_labelling_ab.txt")
+    assert args.window >= 200 and args.rounds >= 5
+    new, parent = open_lib(_lib.LIB_PATH), open_lib(args.parent)
+    libs = (new, parent)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("device: %s" % torch.cuda.get_device_name(0))
+    say("new: %s   parent: %s" % (os.path.relpath(_lib.LIB_PATH, ROOT), os.path.relpath(args.parent, ROOT)))
+    say("")
+    differ, slower = (loss_tables if args.what == "loss" else labelling_tables)(libs, args, say)
+    with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return 1 if differ or slower else 0
 

@@ -103,7 +103,10 @@ def _queries_of_length(rng, x, lens, n_peaky, V, L):
     return out
 
 
-@pytest.mark.parametrize("L", [1, 8, 9, 16, 17, 32, 33, 128])
+QUERY_LENGTHS = [1, 8, 9, 16, 17, 32, 33, 128]       # around every lane layout's limit (scripts/ctc_parent_ab.py runs them too)
+
+
+@pytest.mark.parametrize("L", QUERY_LENGTHS)
 def test_query_lengths_and_lane_layouts(L):
     """S = 2L-1 = 1; 15 / 17 (the 16-lane segment's seam); 31 / 33; 63 / 65 (one position per lane against four); 255.  Two peaky lines
     (substrings of their greedy labellings: real occurrences) and one short dense line (every query has a finite, tiny count), Q = 7

@@ -154,6 +154,40 @@ def test_n1_minus_one_agrees_with_the_ctc_loss(name, regime):
             assert bool((dd <= own.grad_bar[:act[b], b]).all()), (name, b)
 
 
+def test_every_labelling_entry_reports_the_same_forward_score_bits():
+    """ln P_ctc(labels | x) is the same expressions in the same order in ctc_label_sweep of ctc_lattice.h and in the alignment's sum
+    row, so the alignment's scores[..., 1], the edit scores' ctc and the n-best ctc with and without weights hold the same bits.  One batch on the sweep's seams: T 72, B 4, V 7, n 6;
+    columns 1 and 2 are one class and column 6 is -inf in every frame; lens 72, 17, 9 (the first frame apart, PF = TB = 8 frames a
+    block: 9 ends on a block, 17 just past one) and 0; labellings of 0, 1, 31, 32, 33 and 36 labels on every line (S = 63, 65, 67
+    around the one-wave limit; M = 36 gives the S > 64 instantiation its LDS rows).  On the 72-frame line four are feasible and two have
+    no path: the 33 labels hold column 6, and the 32 EQUAL labels need 63 frames, which the 72 offer, so the run that is too long for
+    its line is the same labelling on the lines of 17 and 9 frames, like every L > len there (no run of at most 36 labels exceeds 72
+    frames: 2 * 36 - 1 = 71).  No NaN logits: the alignment guards its sum row against them by design."""
+    from vistaocr_amd import ops
+    T, B, V, n = 72, 4, 7, 6
+    x = torch.randn(T, B, V, generator=torch.Generator().manual_seed(72))
+    x[:, :, 6] = float("-inf")
+    canon = torch.tensor([0, 1, 1, 3, 4, 5, 6], dtype=torch.int32, device="cuda")
+    lens = [72, 17, 9, 0]
+    hyp = [[], [3], [(1, 2, 3, 4, 5)[i % 5] for i in range(31)], [4] * 32,
+           [(3, 5)[i % 2] for i in range(16)] + [6] + [(1, 4)[i % 2] for i in range(16)], [(5, 3, 1, 4, 2)[i % 5] for i in range(36)]]
+    assert [len(h) for h in hyp] == [0, 1, 31, 32, 33, 36]
+    labels, label_lens = nr.pack([hyp] * B, 36, "cuda")
+    xd, ld = x.cuda(), torch.tensor(lens, dtype=torch.int32, device="cuda")
+    w = torch.linspace(-1.0, 1.0, B * n, device="cuda").reshape(B, n).contiguous()
+    al = ops.ctc_align(xd, ld, labels, label_lens, canon)[0][:, :, 1].contiguous()
+    ed = ops.ctc_edit_scores(xd, ld, labels, label_lens, canon)[0]
+    nw = ops.ctc_nbest(xd, ld, labels, label_lens, canon, w)[0]
+    no = ops.ctc_nbest(xd, ld, labels, label_lens, canon)[0]
+    finite = torch.tensor([[1, 1, 1, 1, 0, 1], [1, 1, 0, 0, 0, 0], [1, 1, 0, 0, 0, 0], [1, 0, 0, 0, 0, 0]], dtype=torch.bool)
+    for name, got in (("align", al), ("edit", ed), ("nbest, weights", nw), ("nbest, scores only", no)):
+        got = got.cpu()
+        assert tuple(got.shape) == (B, n) and not bool(torch.isnan(got).any()), name
+        assert bool((torch.isfinite(got) == finite).all()) and bool((got[~finite] == cr.NEG).all()), (name, got)
+        assert float(got[3, 0]) == 0.0, name                                      # no frames, no labels: probability 1
+        assert torch.equal(got.view(torch.int32), al.cpu().view(torch.int32)), (name, got, al)
+
+
 def test_python_entry_shapes_and_errors():
     from vistaocr_amd import ops
     k, ref = _reference("T17")

@@ -22,19 +22,19 @@
 //   S  > 64 : both previous rows in LDS (in the workspace beyond 1663 labels, where they no longer fit), lanes over 64-position chunks, updated in place from the highest chunk down (a chunk reads
 //             only positions that no earlier chunk of the step wrote); the gathered log-probabilities of TB frames are staged into LDS
 //             in one pass of independent loads, so the L2 round trip is paid once per TB frames.
+// The recursion is the one of ctc_label_sweep (ctc_lattice.h), which the edit scores and the n-best gradient run, with the Viterbi row
+// beside it.  It is written out here and not an instantiation of that template: as one, the S > 64 loop compiled to the same
+// instructions at another address and ran 1.4 % slower (profiles/ctc_labelling_ab.txt has the kept form's figures).  PF, TB, the
+// LDS size and the host side in front of the call are the header's.
 // Back pointers take 2 bits per (t, s): two wave ballots (bit 0, bit 1) per (t, 64-position chunk), 16 bytes, written by lane 0.
 // They live in LDS when the line's frames * chunks * 16 bytes fit beside the rows, else in the workspace.  The backtrace is serial (lane 0, one
 // 16-byte read per frame); it yields for label p the first and last frame spent in state 2p+1.  Label scores (peak / sum of the
 // class's frame log-probability over the span) are then computed by lane p % 64 in frame order.
 // Every float is computed by a fixed lane in a fixed order and the only cross-lane operations are shuffles and ballots: results are
 // bit-identical from run to run.
-#include "ctc_align_common.h"
+#include "ctc_lattice.h"
 
 namespace {
-
-constexpr int PF = 8;                        // S <= 64: frames of gathered log-probabilities in flight
-constexpr int TB = 8;                        // S > 64: frames staged per gather pass
-constexpr size_t LDS_BUDGET = 144 * 1024;    // of the 160 KiB per CU
 
 struct BackPtr {
     ulonglong2* lds;
@@ -234,13 +234,12 @@ struct Plan {
     bool ok;
 };
 
-Plan plan_for(int t, int b, int v, int n, int max_label_len) {
+Plan align_plan(int t, int b, int v, int n, int max_label_len) {
     Plan p = {0, 0, 0, false, false, false};
-    if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || n < 1 || n > NMAX || max_label_len < 0 || max_label_len > t) return p;
-    if ((long)t * b * n >= (1L << 31) || (long)b * n * (max_label_len > 0 ? max_label_len : 1) * 2 >= (1L << 31)) return p;
-    p.sp = ((2 * max_label_len + 1 + 63) / 64) * 64;
-    p.rows_floats = p.sp == 64 ? 0 : (size_t)2 * (p.sp + 2) + p.sp + (size_t)TB * p.sp;
-    p.rows_floats = (p.rows_floats + 3) & ~(size_t)3;             // the back pointers behind them are 16-byte words
+    const LabelPlan lp = label_plan(t, b, v, n, max_label_len);
+    if (!lp.ok || (long)b * n * (max_label_len > 0 ? max_label_len : 1) * 2 >= (1L << 31)) return p;
+    p.sp = lp.sp;
+    p.rows_floats = (sweep_floats(p.sp, 2) + 3) & ~(size_t)3;    // the back pointers behind them are 16-byte words
     p.rows_lds = p.rows_floats * 4 <= LDS_BUDGET;
     p.bp_bytes = (size_t)t * (p.sp / 64) * 16;
     p.bp_lds = (p.rows_lds ? p.rows_floats * 4 : 0) + p.bp_bytes <= LDS_BUDGET;
@@ -248,13 +247,10 @@ Plan plan_for(int t, int b, int v, int n, int max_label_len) {
     return p;
 }
 
-// the class log-probabilities in front of the workspace, rounded so that the 16-byte back-pointer words behind them stay aligned
-size_t clp_bytes(int t, int b, int v) { return ((size_t)t * b * v * sizeof(float) + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" size_t vocr_ctc_align_workspace_bytes(int t, int b, int v, int n, int max_label_len) {
-    const Plan p = plan_for(t, b, v, n, max_label_len);
+    const Plan p = align_plan(t, b, v, n, max_label_len);
     if (!p.ok) return 0;
     return clp_bytes(t, b, v) + (p.bp_lds ? 0 : (size_t)b * n * p.bp_bytes) + (p.rows_lds ? 0 : (size_t)b * n * p.rows_floats * 4);
 }
@@ -263,35 +259,23 @@ extern "C" int vocr_ctc_align(const float* logits, const int32_t* lens, int t, i
                               const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
                               float* out_scores, int32_t* out_spans, float* out_label_scores, void* workspace, size_t workspace_bytes,
                               void* stream) {
-    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_scores && out_spans && out_label_scores && workspace,
-                   "vocr_ctc_align: null pointer");
-    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "vocr_ctc_align: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", VMAX, t, b, v);
-    VOCR_CHECK_ARG(n >= 1 && n <= NMAX, "vocr_ctc_align: need 1 <= n <= %d (n=%d)", NMAX, n);
-    VOCR_CHECK_ARG(max_label_len >= 0 && max_label_len <= t && label_stride >= max_label_len,
-                   "vocr_ctc_align: need 0 <= max_label_len <= t and label_stride >= max_label_len (max_label_len=%d t=%d label_stride=%d)",
-                   max_label_len, t, label_stride);
-    const Plan p = plan_for(t, b, v, n, max_label_len);
+    const char* who = "vocr_ctc_align";
+    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_scores && out_spans && out_label_scores && workspace, "%s: null pointer",
+                   who);
+    if (check_labelling_shape(who, t, b, v, n, label_stride, max_label_len) != VOCR_OK) return VOCR_EINVAL;
+    const Plan p = align_plan(t, b, v, n, max_label_len);
     VOCR_CHECK_ARG(p.ok, "vocr_ctc_align: unsupported shape (t=%d b=%d v=%d n=%d max_label_len=%d): t*b*n or b*n*max_label_len too large",
                    t, b, v, n, max_label_len);
     const size_t need = vocr_ctc_align_workspace_bytes(t, b, v, n, max_label_len);
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_align: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        hipError_t e = hipFuncSetAttribute((const void*)ctc_align_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)ctc_align_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
-        if (e != hipSuccess) {
-            vocr_set_error("vocr_ctc_align: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-            return VOCR_ELAUNCH;
-        }
-        lds_ok = true;
-    }
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_align_kernel<false>, (const void*)ctc_align_kernel<true>};
+    if (vocr_allow_dynamic_lds(big, 2, (int)LDS_BUDGET, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     float* clp = (float*)workspace;
     ulonglong2* bp_ws = (ulonglong2*)((char*)workspace + clp_bytes(t, b, v));
     VOCR_CHECK_ARG(p.bp_lds || (((uintptr_t)workspace) & 15) == 0, "vocr_ctc_align: workspace must be 16-byte aligned");
-    class_logprob_rows_kernel<<<vocr_cdiv((long)t * b, ROWS_PER_BLOCK), 256, 0, s>>>(logits, lens, canon, clp, t, b, v);
-    VOCR_CHECK_LAUNCH("vocr_ctc_align(class_logprob)");
+    if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
     // where the longest line's back pointers do not fit, shorter lines still keep theirs in what is left of 64 KiB (two lines per CU)
     const size_t rows_bytes = p.rows_lds ? p.rows_floats * 4 : 0;
     const size_t bp_lds = p.bp_lds ? p.bp_bytes : (rows_bytes < 64 * 1024 ? 64 * 1024 - rows_bytes : 0);

@@ -196,16 +196,9 @@ extern "C" int vocr_ctc_beam_search(const float* logits, const int32_t* lens, in
                    "vocr_ctc_beam_search: lm_weight and insertion_bonus must be finite, prune_logp not NaN");
     const size_t need = vocr_ctc_beam_workspace_bytes(t, b, v, beam, nbest);
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_beam_search: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        const hipError_t e = hipFuncSetAttribute((const void*)ctc_beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 KMAX * VMAX * (int)sizeof(float));
-        if (e != hipSuccess) {
-            vocr_set_error("vocr_ctc_beam_search: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-            return VOCR_ELAUNCH;
-        }
-        lds_ok = true;
-    }
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_beam_kernel};
+    if (vocr_allow_dynamic_lds(big, 1, KMAX * VMAX * (int)sizeof(float), &lds_set, "vocr_ctc_beam_search") != VOCR_OK) return VOCR_ELAUNCH;
     const size_t lds = (size_t)beam * v * sizeof(float);
     ctc_beam_kernel<<<b, BT, lds, (hipStream_t)stream>>>(logits, lens, t, b, v, canon, beam, nbest, any_lm ? lm_logp : nullptr, lm_next,
                                                          lm_eos, any_lm ? lm_states : 1, any_lm ? lm_start : 0, lm_weight,

@@ -11,7 +11,6 @@ namespace ctcbeam {
 
 constexpr int BT = 256;            // threads per line
 constexpr int KMAX = 128;
-constexpr int VMAX = 256;
 
 // order-preserving map of a non-NaN float to uint32 (larger score -> larger key)
 __device__ __forceinline__ unsigned score_key(float s) {
@@ -67,14 +66,10 @@ struct Frame {
     float red[4];
 };
 
-// sanitised canon (an entry that is not a canonical index <= v stands for itself), member chains.  Ends with a barrier.
+// sanitised canon (class_of), member chains.  Ends with a barrier.
 __device__ __forceinline__ void init_classes(const int32_t* __restrict__ canon, int V, Frame& f) {
     const int tid = threadIdx.x;
-    if (tid < V) {
-        int c = canon ? canon[tid] : tid;
-        if (c < 0 || c > tid || (canon && canon[c] != c)) c = tid;
-        f.cls[tid] = c;
-    }
+    if (tid < V) f.cls[tid] = class_of(canon, tid);
     __syncthreads();
     if (tid < V) {
         int nx = -1;

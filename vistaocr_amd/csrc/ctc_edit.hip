@@ -16,13 +16,10 @@
 // ("!=" compares classes).  Every sum cuts a path at its last frame in a given state, so no path is counted twice.
 //
 //   kernel 1  class log-probabilities : class_logprob_rows_kernel of the alignment, once per line.
-//   kernel 2  lattices (ctc_lattice.h): one wave per (line, hypothesis, direction) writes alpha or beta to the workspace, TRANSPOSED
-//                                       ([s][t]: kernel 3 walks one position through the frames).  beta is alpha of the reversed
-//                                       labelling over the reversed frames, so both directions run the same code.  S <= 64: one
-//                                       position per lane, the row in registers, neighbours by shuffles, the gathered
-//                                       log-probabilities prefetched PF frames ahead.  S > 64: the row in LDS, lanes over 64-position
-//                                       chunks updated in place from the highest chunk down, TB frames of gathered log-probabilities
-//                                       staged per pass.  The forward wave also writes ln P_ctc(labels | x).
+//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel: one wave per (line, hypothesis, direction) writes alpha or beta to the
+//                                       workspace, TRANSPOSED ([s][t]: kernel 3 walks one position through the frames), by
+//                                       ctc_label_sweep, which the n-best gradient runs too.  beta is alpha of the reversed labelling over the reversed
+//                                       frames, so both directions run the same code.  The forward wave also writes ln P_ctc(labels | x).
 //   kernel 3  edit scores             : one workgroup per (line, hypothesis, slot p), p = 0 .. max_label_len; thread c owns column c
 //                                       (coalesced class log-probabilities).  One pass over the frames serves the substitution at p,
 //                                       the insertion before p (the same x) and the deletion of p.  The alpha / beta values of a
@@ -34,8 +31,6 @@
 #include "ctc_lattice.h"
 
 namespace {
-
-constexpr size_t LATTICE_BYTES_MAX = (size_t)1 << 31;
 
 // what kernel 3 needs of one frame t: the column's and the blank's class log-probability, alpha[t][2p], alpha[t][2p-1] and
 // beta[t+1][2p+1 .. 2p+3] (-inf where the position does not exist)
@@ -147,30 +142,16 @@ __global__ __launch_bounds__(256) void ctc_edit_scores_kernel(const float* __res
     if (c == 0 && del) *del = p < L ? acc_del.get() : NEG_INF;
 }
 
-struct Plan {
-    int sp;                // extended positions rounded up to 64
-    size_t lds;            // dynamic LDS of the lattice kernel (0 when every labelling fits one wave)
-    size_t lattice_bytes;  // alpha and beta of every (line, hypothesis)
-    bool ok;
-};
-
-Plan plan_for(int t, int b, int v, int n, int max_label_len) {
-    Plan p = {0, 0, 0, false};
-    if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || n < 1 || n > NMAX || max_label_len < 0 || max_label_len > t) return p;
-    if ((long)t * b * n >= (1L << 31) || (long)b * n * (max_label_len + 1) >= (1L << 31)) return p;
-    p.sp = ((2 * max_label_len + 1 + 63) / 64) * 64;
-    p.lds = p.sp == 64 ? 0 : ((size_t)(p.sp + 2) + p.sp + (size_t)TB * p.sp) * 4;
-    p.lattice_bytes = (size_t)b * n * 2 * (2 * (size_t)max_label_len + 1) * t * sizeof(float);
-    p.ok = p.lds <= LDS_BUDGET && p.lattice_bytes <= LATTICE_BYTES_MAX;
-    return p;
+// kernel 3's grid, B * n * (max_label_len + 1) workgroups, is this entry's own limit
+LatticePlan edit_plan(int t, int b, int v, int n, int max_label_len) {
+    if ((long)b * n * (max_label_len + 1) >= (1L << 31)) return LatticePlan{0, 0, 0, false};
+    return lattice_plan(t, b, v, n, max_label_len);
 }
-
-size_t clp_bytes(int t, int b, int v) { return ((size_t)t * b * v * sizeof(float) + 15) & ~(size_t)15; }
 
 }  // namespace
 
 extern "C" size_t vocr_ctc_edit_workspace_bytes(int t, int b, int v, int n, int max_label_len) {
-    const Plan p = plan_for(t, b, v, n, max_label_len);
+    const LatticePlan p = edit_plan(t, b, v, n, max_label_len);
     if (!p.ok) return 0;
     return clp_bytes(t, b, v) + p.lattice_bytes;
 }
@@ -179,37 +160,24 @@ extern "C" int vocr_ctc_edit_scores(const float* logits, const int32_t* lens, in
                                     const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
                                     float* out_ctc, float* out_sub, float* out_del, float* out_ins, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_ctc && out_sub && out_del && out_ins && workspace,
-                   "vocr_ctc_edit_scores: null pointer");
-    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "vocr_ctc_edit_scores: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", VMAX, t,
-                   b, v);
-    VOCR_CHECK_ARG(n >= 1 && n <= NMAX, "vocr_ctc_edit_scores: need 1 <= n <= %d (n=%d)", NMAX, n);
-    VOCR_CHECK_ARG(max_label_len >= 0 && max_label_len <= t && label_stride >= max_label_len,
-                   "vocr_ctc_edit_scores: need 0 <= max_label_len <= t and label_stride >= max_label_len (max_label_len=%d t=%d "
-                   "label_stride=%d)", max_label_len, t, label_stride);
-    const Plan p = plan_for(t, b, v, n, max_label_len);
+    const char* who = "vocr_ctc_edit_scores";
+    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_ctc && out_sub && out_del && out_ins && workspace, "%s: null pointer", who);
+    if (check_labelling_shape(who, t, b, v, n, label_stride, max_label_len) != VOCR_OK) return VOCR_EINVAL;
+    const LatticePlan p = edit_plan(t, b, v, n, max_label_len);
     VOCR_CHECK_ARG(p.ok, "vocr_ctc_edit_scores: unsupported shape (t=%d b=%d v=%d n=%d max_label_len=%d): the lattices of all labellings "
                    "(%zu bytes) must fit %zu bytes and one row of the sweep (%zu bytes) the LDS", t, b, v, n, max_label_len,
                    p.lattice_bytes, LATTICE_BYTES_MAX, p.lds);
     const size_t need = vocr_ctc_edit_workspace_bytes(t, b, v, n, max_label_len);
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_edit_scores: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        const hipError_t e = hipFuncSetAttribute((const void*)ctc_edit_lattice_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)LDS_BUDGET);
-        if (e != hipSuccess) {
-            vocr_set_error("vocr_ctc_edit_scores: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-            return VOCR_ELAUNCH;
-        }
-        lds_ok = true;
-    }
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_lattice_kernel<true>};
+    if (vocr_allow_dynamic_lds(big, 1, (int)LDS_BUDGET, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     float* clp = (float*)workspace;
     float* lat = (float*)((char*)workspace + clp_bytes(t, b, v));
-    class_logprob_rows_kernel<<<vocr_cdiv((long)t * b, ROWS_PER_BLOCK), 256, 0, s>>>(logits, lens, canon, clp, t, b, v);
-    VOCR_CHECK_LAUNCH("vocr_ctc_edit_scores(class_logprob)");
-    ctc_edit_lattice_kernel<true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
-                                                          p.sp, lat, out_ctc);
+    if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
+    ctc_lattice_kernel<true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
+                                                     p.sp, lat, out_ctc);
     VOCR_CHECK_LAUNCH("vocr_ctc_edit_scores(lattices)");
     ctc_edit_scores_kernel<<<b * n * (max_label_len + 1), vocr_cdiv(v, 64) * 64, 0, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n,
                                                                                         label_stride, max_label_len, lat, out_sub,

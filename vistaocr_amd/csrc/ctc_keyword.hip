@@ -422,8 +422,6 @@ __global__ __launch_bounds__(256) void keyword_search_kernel(const float* __rest
 #undef KW_ARGS
 }
 
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 struct Plan {
     size_t rows_bytes;     // one [T * B][V] fp32 matrix: the class log-probabilities, and again the not-class rows
     size_t sums_bytes;     // one [B][T] fp32 matrix: the blank prefix sums, and again the suffix sums
@@ -435,7 +433,7 @@ Plan plan_for(int t, int b, int v, int nq, int max_query_len) {
     Plan p = {0, 0, 0, false};
     if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || nq < 1 || max_query_len < 1 || max_query_len > QLEN_MAX) return p;
     if ((long)t * b * nq >= (1L << 31)) return p;
-    p.rows_bytes = align16((size_t)t * b * v * sizeof(float));
+    p.rows_bytes = clp_bytes(t, b, v);
     p.sums_bytes = align16((size_t)t * b * sizeof(float));
     p.ints_bytes = align16((size_t)(HDR + 2 * (size_t)nq) * sizeof(int32_t));
     p.ok = true;
@@ -477,10 +475,8 @@ extern "C" int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens,
     int32_t* perm = hdr + HDR;
     int32_t* key = perm + nq;
     const int pack = VOCR_EXPERIMENT_INT("VOCR_KWS_PACK", 1);     // 0: every query of up to 32 labels takes a wave of its own
-    const int row_blocks = vocr_cdiv((long)t * b, ROWS_PER_BLOCK);
-    class_logprob_rows_kernel<<<row_blocks, 256, 0, s>>>(logits, lens, canon, clp, t, b, v);
-    VOCR_CHECK_LAUNCH("vocr_ctc_keyword_scores(class_logprob)");
-    not_class_rows_kernel<<<row_blocks, 256, 0, s>>>(logits, lens, canon, notc, t, b, v);
+    if (launch_class_logprob("vocr_ctc_keyword_scores", logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
+    not_class_rows_kernel<<<vocr_cdiv((long)t * b, ROWS_PER_BLOCK), 256, 0, s>>>(logits, lens, canon, notc, t, b, v);
     VOCR_CHECK_LAUNCH("vocr_ctc_keyword_scores(not_class)");
     blank_sums_kernel<<<b, 64, 0, s>>>(clp, lens, t, b, v, pre, suf);
     VOCR_CHECK_LAUNCH("vocr_ctc_keyword_scores(blank_sums)");

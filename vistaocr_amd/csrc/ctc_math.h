@@ -6,6 +6,16 @@
 namespace {
 
 constexpr float NEG_INF = -INFINITY;
+constexpr int VMAX = 256;                    // columns of a row, in every kernel with symbol classes
+
+// The class of column v under canon[V] (NULL: every column its own class): an entry that is not a canonical index <= v stands for
+// itself.  The one statement of the rule, for the beam searches, the labelling scorers and the edit statistics.
+__device__ __forceinline__ int class_of(const int32_t* __restrict__ canon, int v) {
+    if (!canon) return v;
+    int c = canon[v];
+    if (c < 0 || c > v || canon[c] != c) c = v;
+    return c;
+}
 
 // max-shifted log-sum-exp of two / three terms; all -inf stays -inf (never NaN)
 __device__ __forceinline__ float lse2(float a, float b) {

@@ -12,7 +12,7 @@
 // the sums over the hypotheses with a finite score.
 //
 //   kernel 1  class log-probabilities : class_logprob_rows_kernel of the alignment, once per line.
-//   kernel 2  lattices (ctc_lattice.h): the lattice kernel of the edit scores.  With weights: one wave per (line, hypothesis,
+//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel, as the edit scores.  With weights: one wave per (line, hypothesis,
 //                                       direction) writes alpha or beta TRANSPOSED ([s][t]) to the workspace and the forward wave
 //                                       out_ctc.  Without: the forward wave alone, nothing stored.  out_ctc holds the bits of
 //                                       vocr_ctc_edit_scores's either way.
@@ -22,8 +22,8 @@
 //                                       (acc[g][c][k]: consecutive lanes, consecutive banks), reading alpha and beta along t
 //                                       (coalesced, TT * 4 bytes per position).  No two lanes share an accumulator, so there is no
 //                                       reduction inside the loop, no atomic, and the order of every sum is fixed.  Then, frame by
-//                                       frame, the lanes stride over the row's columns: the row's log-softmax again (the expressions
-//                                       of kernel 1: with no classes the member share is exactly 1), the QG partial sums added in
+//                                       frame, the lanes stride over the row's columns: the row's log-softmax again (wave_row_lse, the
+//                                       function kernel 1 calls: with no classes the member share is exactly 1), the QG partial sums added in
 //                                       order, one coalesced store of the row.  Rows t >= lens[b] are written as zeros.
 // A term with alpha or beta at -inf is skipped and a column with p_t(v) = 0 gets share 0, so a class with P_t(c) = 0 never meets a
 // division; a hypothesis with a -inf score is skipped whole, whatever its weight.  A line's rows are computed from that line alone.
@@ -33,7 +33,6 @@ namespace {
 
 constexpr int TT = 16;                       // kernel 3: frames per workgroup
 constexpr int QG = 4;                        // kernel 3: hypothesis groups (TT * QG = 64 lanes)
-constexpr size_t LATTICE_BYTES_MAX = (size_t)1 << 31;
 
 // grid.x = B * ceil(T / TT) (tile fastest), 64 threads.  Dynamic LDS: acc[QG][V][TT] floats.
 __global__ __launch_bounds__(64) void ctc_nbest_grad_kernel(const float* __restrict__ logits, const float* __restrict__ clp,
@@ -90,16 +89,9 @@ __global__ __launch_bounds__(64) void ctc_nbest_grad_kernel(const float* __restr
         }
         const float* xr = logits + row * V;
         const float* cr = clp + row * V;
-        float m = NEG_INF;
-        for (int v = lane; v < V; v += 64) m = fmaxf(m, xr[v]);
-        m = wave_max(m);
-        float sum = 0.f;
-        if (m != NEG_INF)
-            for (int v = lane; v < V; v += 64) sum += expf(xr[v] - m);
-        sum = wave_sum(sum);
-        const float lse = m + logf(sum);
+        const RowLse rl = wave_row_lse(xr, V, lane);
         for (int v = lane; v < V; v += 64) {
-            const float lpv = (m == NEG_INF) ? NEG_INF : xr[v] - lse;
+            const float lpv = row_logprob(rl, xr, v);
             const float* a = acc + (long)class_of(canon, v) * TT + kk;
             float G = a[0];
 #pragma unroll
@@ -110,30 +102,10 @@ __global__ __launch_bounds__(64) void ctc_nbest_grad_kernel(const float* __restr
     }
 }
 
-struct Plan {
-    int sp;                // extended positions rounded up to 64
-    size_t lds;            // dynamic LDS of the lattice kernel (0 when every labelling fits one wave)
-    size_t lattice_bytes;  // alpha and beta of every (line, hypothesis): only a call with weights stores them
-    bool ok;
-};
-
-Plan plan_for(int t, int b, int v, int n, int max_label_len) {
-    Plan p = {0, 0, 0, false};
-    if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || n < 1 || n > NMAX || max_label_len < 0 || max_label_len > t) return p;
-    if ((long)t * b * n >= (1L << 31)) return p;
-    p.sp = ((2 * max_label_len + 1 + 63) / 64) * 64;
-    p.lds = p.sp == 64 ? 0 : ((size_t)(p.sp + 2) + p.sp + (size_t)TB * p.sp) * 4;
-    p.lattice_bytes = (size_t)b * n * 2 * (2 * (size_t)max_label_len + 1) * t * sizeof(float);
-    p.ok = p.lds <= LDS_BUDGET && p.lattice_bytes <= LATTICE_BYTES_MAX;
-    return p;
-}
-
-size_t clp_bytes(int t, int b, int v) { return ((size_t)t * b * v * sizeof(float) + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" size_t vocr_ctc_nbest_workspace_bytes(int t, int b, int v, int n, int max_label_len) {
-    const Plan p = plan_for(t, b, v, n, max_label_len);
+    const LatticePlan p = lattice_plan(t, b, v, n, max_label_len);
     if (!p.ok) return 0;
     return clp_bytes(t, b, v) + p.lattice_bytes;
 }
@@ -142,16 +114,12 @@ extern "C" int vocr_ctc_nbest_grad(const float* logits, const int32_t* lens, int
                                    const int32_t* labels, const int32_t* label_lens, int n, int label_stride, int max_label_len,
                                    const float* weights, float* out_ctc, float* dlogits, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_ctc && workspace, "vocr_ctc_nbest_grad: null pointer");
+    const char* who = "vocr_ctc_nbest_grad";
+    VOCR_CHECK_ARG(logits && lens && labels && label_lens && out_ctc && workspace, "%s: null pointer", who);
     VOCR_CHECK_ARG(!weights == !dlogits, "vocr_ctc_nbest_grad: weights and dlogits go together (weights %s, dlogits %s)",
                    weights ? "given" : "NULL", dlogits ? "given" : "NULL");
-    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "vocr_ctc_nbest_grad: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", VMAX, t,
-                   b, v);
-    VOCR_CHECK_ARG(n >= 1 && n <= NMAX, "vocr_ctc_nbest_grad: need 1 <= n <= %d (n=%d)", NMAX, n);
-    VOCR_CHECK_ARG(max_label_len >= 0 && max_label_len <= t && label_stride >= max_label_len,
-                   "vocr_ctc_nbest_grad: need 0 <= max_label_len <= t and label_stride >= max_label_len (max_label_len=%d t=%d "
-                   "label_stride=%d)", max_label_len, t, label_stride);
-    const Plan p = plan_for(t, b, v, n, max_label_len);
+    if (check_labelling_shape(who, t, b, v, n, label_stride, max_label_len) != VOCR_OK) return VOCR_EINVAL;
+    const LatticePlan p = lattice_plan(t, b, v, n, max_label_len);
     VOCR_CHECK_ARG(p.ok, "vocr_ctc_nbest_grad: unsupported shape (t=%d b=%d v=%d n=%d max_label_len=%d): the lattices of all "
                    "labellings (%zu bytes) must fit %zu bytes and one row of the sweep (%zu bytes) the LDS", t, b, v, n, max_label_len,
                    p.lattice_bytes, LATTICE_BYTES_MAX, p.lds);
@@ -159,33 +127,20 @@ extern "C" int vocr_ctc_nbest_grad(const float* logits, const int32_t* lens, int
     const size_t need = clp_bytes(t, b, v) + (weights ? p.lattice_bytes : 0);
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_nbest_grad: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        hipError_t e = hipFuncSetAttribute((const void*)ctc_edit_lattice_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)LDS_BUDGET);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)ctc_edit_lattice_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_BUDGET);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)ctc_nbest_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
-        if (e != hipSuccess) {
-            vocr_set_error("vocr_ctc_nbest_grad: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-            return VOCR_ELAUNCH;
-        }
-        lds_ok = true;
-    }
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_lattice_kernel<true>, (const void*)ctc_lattice_kernel<false>, (const void*)ctc_nbest_grad_kernel};
+    if (vocr_allow_dynamic_lds(big, 3, (int)LDS_BUDGET, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     float* clp = (float*)workspace;
     float* lat = (float*)((char*)workspace + clp_bytes(t, b, v));
-    class_logprob_rows_kernel<<<vocr_cdiv((long)t * b, ROWS_PER_BLOCK), 256, 0, s>>>(logits, lens, canon, clp, t, b, v);
-    VOCR_CHECK_LAUNCH("vocr_ctc_nbest_grad(class_logprob)");
+    if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
     if (!weights) {
-        ctc_edit_lattice_kernel<false><<<b * n, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride,
-                                                                max_label_len, p.sp, nullptr, out_ctc);
+        ctc_lattice_kernel<false><<<b * n, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
+                                                           p.sp, nullptr, out_ctc);
         VOCR_CHECK_LAUNCH("vocr_ctc_nbest_grad(scores)");
         return VOCR_OK;
     }
-    ctc_edit_lattice_kernel<true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride,
-                                                               max_label_len, p.sp, lat, out_ctc);
+    ctc_lattice_kernel<true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
+                                                          p.sp, lat, out_ctc);
     VOCR_CHECK_LAUNCH("vocr_ctc_nbest_grad(lattices)");
     ctc_nbest_grad_kernel<<<b * vocr_cdiv(t, TT), 64, (size_t)QG * v * TT * sizeof(float), s>>>(
         logits, clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len, lat, out_ctc, weights, dlogits);

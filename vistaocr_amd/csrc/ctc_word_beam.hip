@@ -313,16 +313,10 @@ extern "C" int vocr_ctc_word_beam_search(const float* logits, const int32_t* len
                    "vocr_ctc_word_beam_search: lm_weight and word_bonus must be finite, oov_penalty finite or -inf");
     const size_t need = vocr_ctc_word_beam_workspace_bytes(t, b, v, beam, nbest);
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_word_beam_search: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        const hipError_t e = hipFuncSetAttribute((const void*)ctc_word_beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 KMAX * VMAX * (int)sizeof(float));
-        if (e != hipSuccess) {
-            vocr_set_error("vocr_ctc_word_beam_search: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-            return VOCR_ELAUNCH;
-        }
-        lds_ok = true;
-    }
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_word_beam_kernel};
+    if (vocr_allow_dynamic_lds(big, 1, KMAX * VMAX * (int)sizeof(float), &lds_set, "vocr_ctc_word_beam_search") != VOCR_OK)
+        return VOCR_ELAUNCH;
     WordLm L;
     L.kind = cls_kind; L.tok = cls_tok; L.trie_next = trie_next; L.trie_tok = trie_tok; L.trie_la = trie_la;
     L.off = lm_off; L.succ_tok = lm_succ_tok; L.succ_logp = lm_succ_logp; L.succ_next = lm_succ_next; L.bow = lm_bow; L.back = lm_back;

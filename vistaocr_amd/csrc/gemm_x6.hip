@@ -631,15 +631,9 @@ static int x6_gemm_impl(const char* name, const void* a_planes, int a_rows, int 
                    "%s: the view leaves its plane set", name);
     VOCR_CHECK_ARG(g.b_rt0_alt + p.nct * p.ntiles <= g.RTb && g.a_kk0_alt + g.nkk <= g.KKa && g.b_kk0_alt + g.nkk <= g.KKb,
                    "%s: the second view leaves its plane set", name);
-    static bool lds_ok = false;
-    if (!lds_ok) {
-        if (hipFuncSetAttribute((const void*)gemm_x6_kernel<4, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)gemm_x6_kernel<8, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_LDS) != hipSuccess) {
-            vocr_set_error("%s: hipFuncSetAttribute failed", name);
-            return VOCR_ELAUNCH;
-        }
-        lds_ok = true;
-    }
+    static VocrPerDevice lds_set;                                // one per NP: this function is a template
+    const void* const big[] = {(const void*)gemm_x6_kernel<4, NP>, (const void*)gemm_x6_kernel<8, NP>};
+    if (vocr_allow_dynamic_lds(big, 2, X6_LDS, &lds_set, name) != VOCR_OK) return VOCR_ELAUNCH;
     if (p.nct == 8) x6_launch<8, NP>(g, route, workspace, (hipStream_t)stream);
     else x6_launch<4, NP>(g, route, workspace, (hipStream_t)stream);
     VOCR_CHECK_LAUNCH(name);

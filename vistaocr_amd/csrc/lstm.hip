@@ -2204,15 +2204,9 @@ static int lstm_fwd_impl(const float* xproj, const float* whh_fwd, const float* 
                 if (follow) {
                     // waves 8 - 11 of every workgroup: the next layer's x-projection (xproj_follow_waves); 128 KB of dynamic LDS for their panel
                     constexpr int kPanelBytes = 128 * 64 * 4 * 4;
-                    static bool lds_ok = false;
-                    if (!lds_ok) {
-                        const hipError_t e = hipFuncSetAttribute((const void*)lstm_fwd_chain4w<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPanelBytes);
-                        if (e != hipSuccess) {
-                            vocr_set_error("vocr_lstm_fwd_lead: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
-                            return VOCR_ELAUNCH;
-                        }
-                        lds_ok = true;
-                    }
+                    static VocrPerDevice lds_set;
+                    const void* const big[] = {(const void*)lstm_fwd_chain4w<8, true>};
+                    if (vocr_allow_dynamic_lds(big, 1, kPanelBytes, &lds_set, "vocr_lstm_fwd_lead") != VOCR_OK) return VOCR_ELAUNCH;
                     FollowArgs fa = *follow;
                     fa.done = blk;
                     fa.dbg = (unsigned long long*)workspace;

@@ -1,9 +1,9 @@
-// libvocr: error reporting and ABI/device queries (host only).
+// libvocr: error reporting, ABI/device queries and the per-device dynamic-LDS attribute (host only).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdio.h>
-#include "../../include/vocr.h"
+#include "vocr_common.h"
 
 static thread_local char g_err[512] = "";
 
@@ -12,6 +12,21 @@ void vocr_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+int vocr_allow_dynamic_lds(const void* const* kernels, int n, int bytes, VocrPerDevice* done, const char* who) {
+    int dev = -1;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;      // an index beyond the table: set it every time
+    if (known && done->set[dev]) return VOCR_OK;
+    for (int i = 0; i < n; ++i) {
+        const hipError_t e = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) {
+            vocr_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", who, hipGetErrorString(e));
+            return VOCR_ELAUNCH;
+        }
+    }
+    if (known) done->set[dev] = true;
+    return VOCR_OK;
 }
 
 extern "C" const char* vocr_last_error(void) { return g_err; }

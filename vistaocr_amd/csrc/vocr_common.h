@@ -42,6 +42,15 @@ void vocr_set_error(const char* fmt, ...);
 
 static inline int vocr_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// A kernel that asks for more than 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize, on EVERY device it is
+// launched on.  Sets it to `bytes` for the n kernels of one entry point.  `done` is the caller's own static storage: one flag per
+// device index, so that the attribute is set once per device and a process that drives a second GPU sets it there too.  VOCR_OK, or
+// VOCR_ELAUNCH with the error set under the caller's name `who`.
+struct VocrPerDevice {
+    bool set[64];
+};
+int vocr_allow_dynamic_lds(const void* const* kernels, int n, int bytes, VocrPerDevice* done, const char* who);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
