@@ -605,6 +605,48 @@ int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens, int t, int
                             int max_query_len, float* out_log_count, float* out_best, int32_t* out_span,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC grammar search: the exact probability that a line's text belongs to a regular language (the unweighted half of eesen's decode) ---- */
+/* For every (line b, automaton k) ln P = ln of the sum of P(pi | x) over ALL frame paths pi whose collapsed labelling the automaton
+ * accepts - exact under the CTC model, no beam, no hypothesis, no pruning - and the best single path with its labelling.  Inputs,
+ * classes, blank and the repeat rule are vocr_ctc_align's ("equal" and "different" always compare classes).  The g automata are shared by
+ * all lines and concatenated: automaton k has the states g_state_off[k] .. g_state_off[k+1] of accept[] (non-zero: accepting; local
+ * state 0 is the start) and the arcs g_arc_off[k] .. g_arc_off[k+1] of arc_src / arc_cls / arc_dst (LOCAL state numbers; arc_cls a
+ * non-blank column, any member of its class).  The arcs of one automaton are SORTED by (dst, class, src), so that a state's incoming
+ * arcs are contiguous and grouped by class.  All device int32.  With W[s] = "in s, the last frame was blank or nothing was emitted yet"
+ * and A[a] = "the last frame emitted cls_a on arc a":
+ *   t = 0: W[0] = lp_0(blank), A[a] = lp_0(cls_a) if src_a = 0, everything else -inf;
+ *   t > 0: W'[s] = lp_t(blank) + lse(W[s], A[a'] for every a' with dst_a' = s);
+ *          A'[a] = lp_t(cls_a) + lse(A[a], W[src_a], A[a'] for every a' with dst_a' = src_a and class(cls_a') != class(cls_a));
+ *   ln P = lse(W[s] for accepting s, A[a] for every a with accepting dst_a) after frame lens[b]-1.
+ * The excluded term is CTC's repeat rule: the same class twice in a row needs a blank between, the route through W.  It is evaluated as
+ * lse(prefix, suffix) over the class-sorted incoming arcs, never as a subtraction.  For a DETERMINISTIC automaton every labelling has
+ * one state sequence and P is exactly the probability that the labelling is accepted; for a non-deterministic one it is the sum over
+ * (frame path, automaton path) pairs.  WHAT IT IS NOT: there are no weights on the arcs (no language model), no gradient, and the best
+ * score is the maximum over single PATHS through the product (frame path and automaton path), not the most probable accepted
+ * labelling.  The best path is the same recursion with max, a back pointer per frame and cell in the workspace; a candidate replaces
+ * the choice only when strictly greater - W: stay, then the incoming arcs in arc order; A: stay, then W[src], then the incoming arcs in
+ * arc order; at the end the accepting W cells in state order, then the arc cells in arc order.  Outputs: out_logp[B][g] = ln P;
+ * out_best[B][g] = the best path's score; out_labels[B][g][label_stride] / out_lens[B][g] = its collapsed labelling as canonical
+ * columns (0 behind its end) and its length, -1 where nothing is accepted: the beam searches' layout, label_stride >= t, so the result
+ * goes into vocr_ctc_align and vocr_edit_stats with n = g as it is.  out_best, out_labels and out_lens are all NULL or all given; all
+ * NULL: scores only, no max pass and no back pointers.  lens[b] = 0: ln P = best = 0 if the start state accepts, else -inf.
+ * -inf / -inf / -1, for every line, for an automaton that breaks a rule: 1 <= states <= max_states, 0 <= arcs <= max_arcs, src and dst
+ * in range, 0 < cls < v and not in the blank's class, the sort order; it poisons only its own column.  (The offsets themselves must
+ * point into the arrays.)  -inf logits are legal and never yield NaN.  No floating-point atomics: every lse has a fixed order, results
+ * are bit-identical from run to run, and out_logp has the same bits with and without best paths.  Limits: 2 <= v <= 256, g >= 1,
+ * t * b * g < 2^31, max_states + max_arcs <= 8192 (one workgroup per (line, automaton) keeps two rows and two scans of that many words
+ * in LDS; larger lexicons stay with vocr_ctc_word_beam_search), and with best paths t * b * g * (max_states + max_arcs) * 4 bytes of
+ * back pointers <= 2 GiB.  Workspace (16-byte aligned: class log-probabilities, the plan, the back pointers when want_best) from
+ * vocr_ctc_grammar_workspace_bytes (0 for an unsupported shape); bad arguments and unsupported shapes fail with VOCR_EINVAL before any
+ * launch. */
+size_t vocr_ctc_grammar_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_best);
+int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                            const int32_t* g_state_off, const int32_t* g_arc_off, int g,
+                            const int32_t* arc_src, const int32_t* arc_cls, const int32_t* arc_dst,
+                            const int32_t* accept, int max_states, int max_arcs,
+                            float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- edit statistics: compute_cer_wer of test_on_val (src/textutils.py:264-351, src/train_cnn_lstm.py:32-100) and src/edit_dist_trace.py ---- */
 /* Levenshtein statistics (unit costs) of np (hypothesis, reference) pairs that are already on the device: distances and lengths over
  * characters and over the tokens of form_tokenized_words, and - on request - the operation trace.  Integer arithmetic: every output

@@ -12,6 +12,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from .alphabet import Alphabet, arabic_alphabet, english_alphabet, french_alphabet      # noqa: F401,E402
 from .align import CtcAligner                                                           # noqa: F401,E402
 from .keyword import KeywordHits, KeywordSpotter                                        # noqa: F401,E402
+from .grammar import Grammar, GrammarHits, GrammarMatcher                              # noqa: F401,E402
 from .score import ErrorScorer, ErrorStats, OracleStats                                  # noqa: F401,E402
 from .ctc import CTCLoss                                                                # noqa: F401,E402
 from .risk import MinErrorRateLoss                                                      # noqa: F401,E402
@@ -22,5 +23,5 @@ from .train import FlatClampAdam, make_optimizer, seed_rank, train, train_async 
 from .dataset import OcrDataset                                                         # noqa: F401,E402
 
 __all__ = ["Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "ArgmaxDecoder", "BeamDecoder",
-           "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "ErrorScorer", "ErrorStats", "OracleStats",
+           "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "Grammar", "GrammarMatcher", "GrammarHits", "ErrorScorer", "ErrorStats", "OracleStats",
            "CnnOcrModel", "FlatClampAdam", "make_optimizer", "seed_rank", "train", "train_async", "OcrDataset"]

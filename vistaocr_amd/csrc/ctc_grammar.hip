@@ -1,0 +1,522 @@
+// CTC grammar search: for every (line, automaton) the exact probability that the line's collapsed labelling is accepted by a finite
+// automaton over the symbol classes, ln P = ln of the sum over all V^len frame paths whose labelling the automaton accepts, and the
+// best single (frame path, automaton path) with its labelling.  No beam, no pruning: one sweep over the product of the CTC topology
+// with the automaton, frames x (states + arcs) cells.  Conventions are vocr_ctc_align's: blank = 0, classes from canon[V].
+//
+// An automaton has states 0 .. S-1 (0 the start), accept[s], and arcs a = (src, cls, dst) with non-blank labels, sorted by
+// (dst, class, src): the incoming arcs of a state are contiguous and grouped by class.  W[s]: in s, the last frame was blank (or
+// nothing was emitted yet); A[a]: the last frame emitted cls_a on arc a.
+//   t = 0 :  W[0] = lp_0(blank), A[a] = lp_0(cls_a) if src_a = 0; everything else -inf
+//   t > 0 :  W'[s] = lp_t(blank) + lse(W[s], A[a'] for every a' into s)
+//            A'[a] = lp_t(cls_a) + lse(A[a], W[src_a], A[a'] for every a' into src_a whose class is not cls_a's)
+//   ln P  =  lse(W[s] for accepting s, A[a] for accepting dst_a) after the last frame
+// and the same with max for the best path, one back pointer per cell and frame in the workspace.
+// TIE RULE (a candidate replaces the choice only when STRICTLY greater): W: stay, then the incoming arcs in arc order; A: stay, then
+// W[src], then the incoming arcs in arc order; at the end the accepting W cells in state order, then the arc cells in arc order.
+//
+//   kernel 1  class log-probabilities : class_logprob_rows_kernel of the alignment.
+//   kernel 2  plan                    : one workgroup per automaton validates it and writes, per state, the range of its incoming arcs
+//                                       and, per arc, its source, its class and where in the source's incoming arcs the group of its
+//                                       own class begins and ends (binary searches over the sorted arcs); and the list of the states
+//                                       with 64 or more incoming arcs, in state order.
+//   kernel 3  sweep <sum>, <max>      : one workgroup per (line, automaton), sequential over frames, two rows ping-ponging in LDS; the
+//                                       automaton's plan is copied into LDS too where it fits beside them (every frame reads all of it).
+//             phase 1: per state the exclusive prefix and the inclusive suffix lse (max pass: arg max) over its incoming arcs, so that
+//             "all incoming arcs but the group of class c" is lse(prefix at the group's begin, suffix at its end): never a
+//             subtraction, O(E) per frame.  A state with fewer than 64 incoming arcs is scanned by one lane, a state with more by a
+//             wave (the plan's list, dealt out to the waves in turn), 64 arcs at a time, with (max, sum) pairs through shuffles.
+//             phase 2: every W and A cell from the old row and the scans.
+// Every float is computed by a fixed lane in a fixed order (no atomics): results are bit-identical from run to run, and the sum pass is
+// the same launch with or without best paths.
+#include "ctc_align_common.h"
+
+namespace {
+
+constexpr int GN_MAX = 8192;                 // states + arcs of one automaton: two rows and two scans of that many words in LDS
+constexpr int WAVE_DEG = 64;                 // incoming arcs from which on a state is scanned by a wave, not by a lane
+constexpr int NT_SMALL = 256, NT_BIG = 1024; // threads of a sweep workgroup; NT_BIG when the call's largest automaton exceeds N_SMALL cells
+constexpr int N_SMALL = 2048;
+constexpr size_t BP_MAX_BYTES = (size_t)1 << 31;
+constexpr size_t LDS_DYN_MAX = 160 * 1024 - 13 * 1024;     // what a sweep workgroup may ask for beside its static 12.1 KiB
+
+// words of one automaton's list of wave-scanned states: their number, then the states (each has at least WAVE_DEG arcs of its own)
+__host__ __device__ constexpr int big_stride(int max_arcs) { return max_arcs / WAVE_DEG + 2; }
+
+// lower bound over one automaton's arcs: the first i in [lo, hi) with key(i) >= want
+template <class Key>
+__device__ __forceinline__ int lower_bound(int lo, int hi, int want, Key key) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key(mid) < want) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// grid.x = G, 256 threads.  flags[k] = 1 for an automaton that breaks a rule (nothing else is written for it).  st[k][s] = {first,
+// end} of the incoming arcs of s; meta[k][a] = {src, class column, xa, xb}: the other classes' incoming arcs of src are those before
+// xa (read: the exclusive prefix at xa; -1: none) and from xb on (the inclusive suffix at xb; -1: none).
+__global__ __launch_bounds__(256) void grammar_plan_kernel(const int32_t* __restrict__ canon, const int32_t* __restrict__ g_state_off,
+                                                           const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_src,
+                                                           const int32_t* __restrict__ arc_cls, const int32_t* __restrict__ arc_dst, int V,
+                                                           int max_states, int max_arcs, int32_t* __restrict__ flags,
+                                                           int2* __restrict__ st, int4* __restrict__ meta, int32_t* __restrict__ big_all) {
+    __shared__ int s_wcnt[4];
+    __shared__ int s_base;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const int s0 = g_state_off[k], a0 = g_arc_off[k];
+    const long S_ = (long)g_state_off[k + 1] - s0, E_ = (long)g_arc_off[k + 1] - a0;
+    if (s0 < 0 || a0 < 0 || S_ < 1 || S_ > max_states || E_ < 0 || E_ > max_arcs) {
+        if (tid == 0) flags[k] = 1;
+        return;
+    }
+    const int S = (int)S_, E = (int)E_;
+    const int32_t* src = arc_src + a0;
+    const int32_t* cls = arc_cls + a0;
+    const int32_t* dst = arc_dst + a0;
+    auto cls_of = [&](int i) { return class_of(canon, min(max(cls[i], 0), V - 1)); };
+    int bad = 0;
+    for (int i = tid; i < E; i += 256) {
+        const int c = cls_of(i);
+        bad |= src[i] < 0 || src[i] >= S || dst[i] < 0 || dst[i] >= S || cls[i] <= 0 || cls[i] >= V || c == 0;
+        if (i > 0) {
+            const int cp = cls_of(i - 1);
+            bad |= dst[i - 1] > dst[i] || (dst[i - 1] == dst[i] && (cp > c || (cp == c && src[i - 1] > src[i])));
+        }
+    }
+    if (__syncthreads_or(bad)) {
+        if (tid == 0) flags[k] = 1;
+        return;
+    }
+    if (tid == 0) {
+        flags[k] = 0;
+        s_base = 0;
+    }
+    auto dst_key = [&](int i) { return dst[i]; };
+    // the states' ranges, and the list of the states a wave scans, in state order: big[0] their number, big[1 ..] the states
+    int32_t* big = big_all + (long)k * big_stride(max_arcs);
+    const int lane = tid & 63, w = tid >> 6;
+    for (int first = 0; first < S; first += 256) {
+        const int s = first + tid;
+        int lo = 0, hi = 0;
+        if (s < S) {
+            lo = lower_bound(0, E, s, dst_key);
+            hi = lower_bound(0, E, s + 1, dst_key);
+            st[(long)k * max_states + s] = make_int2(lo, hi);
+        }
+        const bool is_big = hi - lo >= WAVE_DEG;
+        const unsigned long long mask = __ballot(is_big);
+        if (lane == 0) s_wcnt[w] = __popcll(mask);
+        __syncthreads();
+        int base = s_base;
+        for (int j = 0; j < w; ++j) base += s_wcnt[j];
+        if (is_big) big[1 + base + __popcll(mask & ((1ull << lane) - 1ull))] = s;
+        __syncthreads();
+        if (tid == 0) s_base += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        __syncthreads();
+    }
+    if (tid == 0) big[0] = s_base;
+    for (int i = tid; i < E; i += 256) {
+        const int s = src[i], c = cls_of(i);
+        const int lo = lower_bound(0, E, s, dst_key), hi = lower_bound(0, E, s + 1, dst_key);
+        const int g0 = lower_bound(lo, hi, c, cls_of), g1 = lower_bound(lo, hi, c + 1, cls_of);
+        int xa = g0 > lo ? g0 : -1, xb = g1 < hi ? g1 : -1;
+        if (g0 == g1) { xa = -1; xb = lo < hi ? lo : -1; }        // no arc of that class comes in: the whole range, as one suffix
+        meta[(long)k * max_arcs + i] = make_int4(s, c, xa, xb);
+    }
+}
+
+// one partial result of a scan: the sum pass keeps a logsumexp as (max m, sum s of exp(x - m)), the max pass (value m, arc i)
+struct GAcc {
+    float m, s;
+    int i;
+};
+
+__device__ __forceinline__ GAcc g_none() { return {NEG_INF, 0.f, -1}; }
+__device__ __forceinline__ GAcc g_elem(float v, int i) { return {v, v == NEG_INF ? 0.f : 1.f, i}; }
+
+// l covers lower arc (cell) indices than r.  max pass: the earlier wins a tie
+template <bool BEST>
+__device__ __forceinline__ GAcc g_join(const GAcc& l, const GAcc& r) {
+    if (BEST) return r.m > l.m ? r : l;
+    if (r.m == NEG_INF) return l;
+    if (l.m == NEG_INF) return r;
+    const float e = expf(-fabsf(l.m - r.m));
+    GAcc o;
+    o.m = fmaxf(l.m, r.m);
+    o.s = l.m >= r.m ? l.s + r.s * e : l.s * e + r.s;
+    o.i = -1;
+    return o;
+}
+
+template <bool BEST>
+__device__ __forceinline__ GAcc g_shfl_up(const GAcc& a, int o) {
+    GAcc r;
+    r.m = __shfl_up(a.m, o, 64);
+    r.s = BEST ? 0.f : __shfl_up(a.s, o, 64);
+    r.i = BEST ? __shfl_up(a.i, o, 64) : -1;
+    return r;
+}
+template <bool BEST>
+__device__ __forceinline__ GAcc g_shfl_down(const GAcc& a, int o) {
+    GAcc r;
+    r.m = __shfl_down(a.m, o, 64);
+    r.s = BEST ? 0.f : __shfl_down(a.s, o, 64);
+    r.i = BEST ? __shfl_down(a.i, o, 64) : -1;
+    return r;
+}
+template <bool BEST>
+__device__ __forceinline__ GAcc g_shfl(const GAcc& a, int lane) {
+    GAcc r;
+    r.m = __shfl(a.m, lane, 64);
+    r.s = BEST ? 0.f : __shfl(a.s, lane, 64);
+    r.i = BEST ? __shfl(a.i, lane, 64) : -1;
+    return r;
+}
+
+// (a single term: ln 1 = 0, the same bits without the logarithm - every state of a trie)
+__device__ __forceinline__ float g_value(const GAcc& a) { return (a.m == NEG_INF || a.s == 1.f) ? a.m : a.m + logf(a.s); }
+
+// a scan entry: the sum pass stores the logsumexp, the max pass the arc of the maximum (its value is read from the row again)
+template <bool BEST>
+__device__ __forceinline__ void g_store(float* __restrict__ p, int i, const GAcc& a) {
+    if (BEST) reinterpret_cast<int*>(p)[i] = a.i;
+    else p[i] = g_value(a);
+}
+
+// ... read back: the value, and in the max pass the arc it came from (-1: none)
+template <bool BEST>
+__device__ __forceinline__ float g_read(const float* __restrict__ p, int i, const float* __restrict__ A, int& arc) {
+    arc = -1;
+    if (i < 0) return NEG_INF;
+    if (!BEST) return p[i];
+    arc = reinterpret_cast<const int*>(p)[i];
+    return arc < 0 ? NEG_INF : A[arc];
+}
+
+// the scans of one state's incoming arcs [lo, hi) by one lane
+template <bool BEST>
+__device__ __forceinline__ void lane_scan(const float* __restrict__ A, float* __restrict__ pre, float* __restrict__ suf, int lo, int hi) {
+    GAcc acc = g_none();
+    for (int i = lo; i < hi; ++i) {
+        g_store<BEST>(pre, i, acc);
+        acc = g_join<BEST>(acc, g_elem(A[i], i));
+    }
+    acc = g_none();
+    for (int i = hi - 1; i >= lo; --i) {
+        acc = g_join<BEST>(g_elem(A[i], i), acc);
+        g_store<BEST>(suf, i, acc);
+    }
+}
+
+// ... and by a whole wave (lo, hi wave-uniform): 64 arcs at a time, Hillis-Steele over the lanes, the earlier chunks carried along
+template <bool BEST>
+__device__ __forceinline__ void wave_scan(const float* __restrict__ A, float* __restrict__ pre, float* __restrict__ suf, int lo, int hi,
+                                          int lane) {
+    GAcc carry = g_none();
+    for (int c0 = lo; c0 < hi; c0 += 64) {
+        const int i = c0 + lane;
+        GAcc x = i < hi ? g_elem(A[i], i) : g_none();
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const GAcc u = g_shfl_up<BEST>(x, o);
+            if (lane >= o) x = g_join<BEST>(u, x);
+        }
+        GAcc ex = g_shfl_up<BEST>(x, 1);
+        if (lane == 0) ex = g_none();
+        if (i < hi) g_store<BEST>(pre, i, g_join<BEST>(carry, ex));
+        carry = g_join<BEST>(carry, g_shfl<BEST>(x, 63));
+    }
+    carry = g_none();
+    for (int c1 = hi; c1 > lo; c1 -= 64) {
+        const int i = c1 - 64 + lane;
+        GAcc x = i >= lo ? g_elem(A[i], i) : g_none();
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const GAcc u = g_shfl_down<BEST>(x, o);
+            if (lane + o < 64) x = g_join<BEST>(x, u);
+        }
+        if (i >= lo) g_store<BEST>(suf, i, g_join<BEST>(x, carry));
+        carry = g_join<BEST>(g_shfl<BEST>(x, 0), carry);
+    }
+}
+
+// grid.x = B * G, NT_SMALL or NT_BIG threads, dynamic LDS: two rows of maxN cells (states, then arcs), the two scans (maxN words
+// each, only E used) and two staged rows of class log-probabilities.  out: out_logp (sum pass) or out_best (max pass).
+template <bool BEST>
+__global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __restrict__ clp, const int32_t* __restrict__ lens,
+                                                             const int32_t* __restrict__ g_state_off, const int32_t* __restrict__ g_arc_off,
+                                                             const int32_t* __restrict__ arc_dst, const int32_t* __restrict__ accept,
+                                                             const int32_t* __restrict__ flags, const int2* __restrict__ st_all,
+                                                             const int4* __restrict__ meta_all, const int32_t* __restrict__ big_all,
+                                                             int stage, int T, int B, int V, int G, int max_states, int max_arcs,
+                                                             float* __restrict__ out, int32_t* __restrict__ bp_all,
+                                                             int32_t* __restrict__ out_labels, int32_t* __restrict__ out_lens,
+                                                             int label_stride) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float r_m[NT_BIG];
+    __shared__ float r_s[NT_BIG];
+    __shared__ int r_i[NT_BIG];
+    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int blk = blockIdx.x, b = blk / G, k = blk - b * G;
+    const int maxN = max_states + max_arcs;
+    int32_t* lab = BEST ? out_labels + (long)blk * label_stride : nullptr;
+    if (flags[k]) {                                                // an invalid automaton poisons its own column
+        if (tid == 0) {
+            out[blk] = NEG_INF;
+            if (BEST) out_lens[blk] = -1;
+        }
+        if (BEST)
+            for (int p = tid; p < label_stride; p += NT) lab[p] = 0;
+        return;
+    }
+    const int S = g_state_off[k + 1] - g_state_off[k], E = g_arc_off[k + 1] - g_arc_off[k], N = S + E;
+    const int32_t* acc_s = accept + g_state_off[k];
+    const int32_t* dst = arc_dst + g_arc_off[k];
+    const int2* st = st_all + (long)k * max_states;
+    const int4* meta = meta_all + (long)k * max_arcs;
+    const int32_t* bigs = big_all + (long)k * big_stride(max_arcs);
+    const int nbig = *bigs++;
+    const int len = min(max(lens[b], 0), T);
+    if (stage) {                                                   // the plan of this automaton in LDS: every frame reads all of it
+        int4* lm = reinterpret_cast<int4*>(sm + 4 * maxN + 2 * VMAX);
+        int2* ls = reinterpret_cast<int2*>(lm + max_arcs);
+        int32_t* lb = reinterpret_cast<int32_t*>(ls + max_states);
+        for (int i = tid; i < E; i += NT) lm[i] = meta[i];
+        for (int i = tid; i < S; i += NT) ls[i] = st[i];
+        for (int i = tid; i < nbig; i += NT) lb[i] = bigs[i];
+        meta = lm;
+        st = ls;
+        bigs = lb;
+        __syncthreads();
+    }
+    float* row0 = sm;
+    float* row1 = sm + maxN;
+    float* pre = sm + 2 * maxN;
+    float* suf = sm + 3 * maxN;
+    float* lprow = sm + 4 * maxN;                                  // [2][VMAX]
+    int32_t* bp = BEST ? bp_all + (long)blk * T * maxN : nullptr;  // [len][N]: the cell of frame t-1 that cell c of frame t came from
+    const long tstride = (long)B * V;
+    const float* lpb = clp + (long)b * V;
+
+    if (len > 0) {
+        if (tid < V) lprow[tid] = lpb[tid];
+        __syncthreads();
+        for (int c = tid; c < N; c += NT) {
+            float v = NEG_INF;
+            if (c == 0) v = lprow[0];
+            else if (c >= S) {
+                const int4 m = meta[c - S];
+                if (m.x == 0) v = lprow[m.y];
+            }
+            row0[c] = v;
+        }
+        __syncthreads();
+    }
+    float* cur = row0;
+    float* nxt = row1;
+    for (int t = 1; t < len; ++t) {
+        const float* A = cur + S;
+        const float next_lp = tid < V ? lpb[t * tstride + tid] : 0.f;          // this frame's row: in LDS after phase 1
+        // phase 1: the scans of every state's incoming arcs
+        for (int s = tid; s < S; s += NT) {
+            const int2 io = st[s];
+            const int D = io.y - io.x;
+            if (D > 0 && D < WAVE_DEG) lane_scan<BEST>(A, pre, suf, io.x, io.y);
+        }
+        for (int kb = wave; kb < nbig; kb += NT >> 6) {            // the states of many incoming arcs, dealt out to the waves
+            const int2 io = st[bigs[kb]];
+            wave_scan<BEST>(A, pre, suf, __builtin_amdgcn_readfirstlane(io.x), __builtin_amdgcn_readfirstlane(io.y), lane);
+        }
+        float* lpr = lprow + (t & 1) * VMAX;
+        if (tid < V) lpr[tid] = next_lp;
+        __syncthreads();
+        // phase 2: every cell
+        for (int c = tid; c < N; c += NT) {
+            float v;
+            int from = c;
+            if (c < S) {
+                const int2 io = st[c];
+                int arc;
+                const float inc = g_read<BEST>(suf, io.y > io.x ? io.x : -1, A, arc);
+                const float w = cur[c];
+                if (BEST) {
+                    v = w;
+                    if (inc > v) { v = inc; from = S + arc; }
+                } else {
+                    v = lse2(w, inc);
+                }
+                v += lpr[0];
+            } else {
+                const int4 m = meta[c - S];
+                int arc_a, arc_b;
+                const float self = cur[c], w = cur[m.x];
+                const float pa = g_read<BEST>(pre, m.z, A, arc_a), pb = g_read<BEST>(suf, m.w, A, arc_b);
+                if (BEST) {
+                    v = self;
+                    if (w > v) { v = w; from = m.x; }
+                    if (pa > v) { v = pa; from = S + arc_a; }
+                    if (pb > v) { v = pb; from = S + arc_b; }
+                } else {
+                    const float mx = fmaxf(fmaxf(self, w), fmaxf(pa, pb));
+                    v = mx == NEG_INF ? NEG_INF : logf(expf(self - mx) + expf(w - mx) + expf(pa - mx) + expf(pb - mx)) + mx;
+                }
+                v += lpr[m.y];
+            }
+            nxt[c] = v;
+            if (BEST) bp[(long)t * N + c] = from;
+        }
+        __syncthreads();
+        float* sw = cur;
+        cur = nxt;
+        nxt = sw;
+    }
+
+    // the end: accepting W cells in state order, then arc cells with an accepting destination in arc order
+    GAcc acc = g_none();
+    if (len > 0) {
+        for (int c = tid; c < N; c += NT) {
+            const bool fin = c < S ? acc_s[c] != 0 : acc_s[dst[c - S]] != 0;
+            if (fin) acc = g_join<BEST>(acc, g_elem(cur[c], c));
+        }
+    } else if (tid == 0 && acc_s[0] != 0) {
+        acc = g_elem(0.f, 0);
+    }
+    r_m[tid] = acc.m;
+    r_s[tid] = acc.s;
+    r_i[tid] = acc.i;
+    __syncthreads();
+    for (int o = NT >> 1; o > 0; o >>= 1) {
+        if (tid < o) {
+            const GAcc l = {r_m[tid], r_s[tid], r_i[tid]}, r = {r_m[tid + o], r_s[tid + o], r_i[tid + o]};
+            GAcc j;
+            if (BEST) j = (r.m > l.m || (r.m == l.m && r.i >= 0 && (l.i < 0 || r.i < l.i))) ? r : l;   // the lower cell wins a tie
+            else j = g_join<false>(l, r);
+            r_m[tid] = j.m;
+            r_s[tid] = j.s;
+            r_i[tid] = j.i;
+        }
+        __syncthreads();
+    }
+    if (!BEST) {
+        if (tid == 0) out[blk] = g_value({r_m[0], r_s[0], -1});
+        return;
+    }
+    // the best path, backwards: a label wherever an arc cell is entered from another cell
+    const float best = r_m[0];
+    __shared__ int s_len;
+    if (tid == 0) {
+        out[blk] = best;
+        int L = -1;
+        if (best != NEG_INF) {
+            L = 0;
+            int c = r_i[0];
+            for (int t = len - 1; t >= 0; --t) {
+                const int from = t > 0 ? bp[(long)t * N + c] : -1;
+                if (c >= S && from != c) lab[L++] = meta[c - S].y;
+                c = from;
+            }
+        }
+        out_lens[blk] = L;
+        s_len = max(L, 0);
+    }
+    __syncthreads();
+    const int L = s_len;
+    for (int p = tid; p < L / 2; p += NT) {                        // the walk wrote the labels last first
+        const int u = lab[p];
+        lab[p] = lab[L - 1 - p];
+        lab[L - 1 - p] = u;
+    }
+    for (int p = L + tid; p < label_stride; p += NT) lab[p] = 0;
+}
+
+struct Plan {
+    size_t flags_bytes, st_bytes, meta_bytes, big_bytes, bp_bytes;
+    int threads;
+    size_t lds;
+    int stage;             // the automaton's plan is copied into LDS (it fits beside the rows)
+    bool ok;
+    size_t plan_bytes() const { return flags_bytes + st_bytes + meta_bytes + big_bytes; }
+};
+
+Plan plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want_best) {
+    Plan p = {0, 0, 0, 0, 0, 0, 0, 0, false};
+    if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || g < 1 || max_states < 1 || max_arcs < 0) return p;
+    if ((long)max_states + max_arcs > GN_MAX || (long)t * b * g >= (1L << 31)) return p;
+    const size_t n = (size_t)max_states + max_arcs;
+    p.flags_bytes = align16((size_t)g * sizeof(int32_t));
+    p.st_bytes = align16((size_t)g * max_states * sizeof(int2));
+    p.meta_bytes = align16((size_t)g * max_arcs * sizeof(int4));
+    p.big_bytes = align16((size_t)g * big_stride(max_arcs) * sizeof(int32_t));
+    if (want_best) {
+        p.bp_bytes = (size_t)t * b * g * n * sizeof(int32_t);
+        if (p.bp_bytes > BP_MAX_BYTES) return p;
+        p.bp_bytes = align16(p.bp_bytes);
+    }
+    p.threads = n > N_SMALL ? NT_BIG : NT_SMALL;
+    p.lds = (4 * n + 2 * VMAX) * sizeof(float);
+    const size_t staged = align16((size_t)max_arcs * sizeof(int4) + (size_t)max_states * sizeof(int2) + (size_t)big_stride(max_arcs) * sizeof(int32_t));
+    if (p.lds + staged <= LDS_DYN_MAX) {
+        p.stage = 1;
+        p.lds += staged;
+    }
+    p.ok = true;
+    return p;
+}
+
+}  // namespace
+
+extern "C" size_t vocr_ctc_grammar_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_best) {
+    const Plan p = plan_for(t, b, v, g, max_states, max_arcs, want_best);
+    if (!p.ok) return 0;
+    return clp_bytes(t, b, v) + p.plan_bytes() + p.bp_bytes;
+}
+
+extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                       const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
+                                       const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, int max_states, int max_arcs,
+                                       float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "vocr_ctc_grammar_scores";
+    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "%s: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", who, VMAX, t, b, v);
+    VOCR_CHECK_ARG(g >= 1, "%s: need g >= 1 (g=%d)", who, g);
+    VOCR_CHECK_ARG(max_states >= 1 && max_arcs >= 0 && (long)max_states + max_arcs <= GN_MAX,
+                   "%s: need max_states >= 1, max_arcs >= 0 and max_states + max_arcs <= %d (max_states=%d max_arcs=%d)", who, GN_MAX,
+                   max_states, max_arcs);
+    const bool any_best = out_best || out_labels || out_lens, all_best = out_best && out_labels && out_lens;
+    VOCR_CHECK_ARG(any_best == all_best, "%s: out_best, out_labels and out_lens must be all NULL or all given", who);
+    VOCR_CHECK_ARG(!all_best || label_stride >= t, "%s: need label_stride >= t (label_stride=%d t=%d)", who, label_stride, t);
+    const Plan p = plan_for(t, b, v, g, max_states, max_arcs, all_best ? 1 : 0);
+    VOCR_CHECK_ARG(p.ok, "%s: unsupported shape (t=%d b=%d v=%d g=%d max_states=%d max_arcs=%d): t*b*g must stay below 2^31 and the back "
+                   "pointers, t*b*g*(max_states+max_arcs)*4 bytes, within 2 GiB", who, t, b, v, g, max_states, max_arcs);
+    VOCR_CHECK_ARG(logits && lens && g_state_off && g_arc_off && accept && out_logp && workspace && (max_arcs == 0 || (arc_src && arc_cls && arc_dst)),
+                   "%s: null pointer", who);
+    const size_t need = clp_bytes(t, b, v) + p.plan_bytes() + p.bp_bytes;
+    VOCR_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    VOCR_CHECK_ARG((((uintptr_t)workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_grammar_kernel<false>, (const void*)ctc_grammar_kernel<true>};
+    if (vocr_allow_dynamic_lds(big, 2, (int)LDS_DYN_MAX, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
+    char* ws = (char*)workspace;
+    float* clp = (float*)ws;
+    int32_t* flags = (int32_t*)(ws + clp_bytes(t, b, v));
+    int2* st = (int2*)((char*)flags + p.flags_bytes);
+    int4* meta = (int4*)((char*)st + p.st_bytes);
+    int32_t* bigs = (int32_t*)((char*)meta + p.meta_bytes);
+    int32_t* bp = (int32_t*)((char*)bigs + p.big_bytes);
+    if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
+    grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, flags, st, meta,
+                                          bigs);
+    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(plan)");
+    ctc_grammar_kernel<false><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs, p.stage, t, b,
+                                                             v, g, max_states, max_arcs, out_logp, nullptr, nullptr, nullptr, 0);
+    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(sum)");
+    if (all_best) {
+        ctc_grammar_kernel<true><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs, p.stage, t,
+                                                                b, v, g, max_states, max_arcs, out_best, bp, out_labels, out_lens, label_stride);
+        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(max)");
+    }
+    return VOCR_OK;
+}

@@ -1,0 +1,535 @@
+"""CTC grammar search on the GPU (vocr_ctc_grammar_scores): what is the probability that this line's text belongs to a given regular
+language - a date, an amount, one of these 500 part numbers, "contains the word X" - and what is the best reading that does, asked of
+the network's output itself.
+
+WHAT THE NUMBER IS: for a line and a grammar (a deterministic finite automaton over the alphabet's symbol classes), the probability
+under the CTC model that the line's collapsed labelling is accepted: the exact sum over ALL frame paths, no beam, no hypothesis, no
+pruning.  WHAT IT IS NOT: there are no weights on the arcs (no language model, no n-gram), there is no gradient, and the "best" result is
+the best single PATH through the grammar (frame path and state sequence), not the most probable accepted LABELLING (which would sum the
+paths of each labelling first).  Characters are compared as the alphabet's symbol strings: indices with the same string are one class
+and share an arc.  An automaton of more than 8192 states + arcs does not fit the kernel; larger lexicons stay with WordBeamDecoder."""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .align import one_copy
+from .textutils import utf8_to_uxxxx, uxxxx_to_utf8
+
+GrammarHits = namedtuple("GrammarHits", "logp prob best_logp best_labels best_text")
+
+
+def _classes(alphabet):
+    """(canon list, sorted list of the non-blank classes)."""
+    canon = alphabet.canonical_indices()
+    return canon, sorted({c for c in canon[1:] if c != 0})
+
+
+def _class_of_char(alphabet, canon, ch, where):
+    tok = utf8_to_uxxxx(ch, output_array=True)[0]
+    k = alphabet.char_to_idx.get(tok)
+    if k is None or canon[k] == 0:
+        raise ValueError("%s: the symbol %r (%s) is not in the alphabet" % (where, ch, tok))
+    return canon[k]
+
+
+def _labels(alphabet, canon, text, where):
+    """A string (utf-8) or a sequence of alphabet indices as a list of classes."""
+    if isinstance(text, str):
+        return [_class_of_char(alphabet, canon, ch, where) for ch in text]
+    out = []
+    for v in text:
+        v = int(v)
+        if v <= 0 or v >= len(canon) or canon[v] == 0:
+            raise ValueError("%s: %d is not a non-blank alphabet index" % (where, v))
+        out.append(canon[v])
+    return out
+
+
+# ---- the regular-expression parser: pattern -> tree.  Nodes: ("set", frozenset of classes), ("cat", [nodes]), ("alt", [nodes]),
+# ("rep", node, lo, hi or None)
+class _Parser(object):
+    def __init__(self, alphabet, pattern):
+        self.alphabet, self.p, self.i = alphabet, pattern, 0
+        self.canon, self.all = _classes(alphabet)
+        self.where = "regex %r" % pattern
+
+    def fail(self, what):
+        raise ValueError("%s: %s at position %d" % (self.where, what, self.i))
+
+    def peek(self):
+        return self.p[self.i] if self.i < len(self.p) else None
+
+    def cls(self, ch):
+        return _class_of_char(self.alphabet, self.canon, ch, self.where)
+
+    def digits(self):
+        d = [self.alphabet.char_to_idx.get("u%04x" % (0x30 + k)) for k in range(10)]
+        d = frozenset(self.canon[k] for k in d if k is not None)
+        if not d:
+            self.fail("\\d: the alphabet has no digits")
+        return d
+
+    def parse(self):
+        node = self.alt()
+        if self.i != len(self.p):
+            self.fail("unbalanced ')'")
+        return node
+
+    def alt(self):
+        parts = [self.cat()]
+        while self.peek() == "|":
+            self.i += 1
+            parts.append(self.cat())
+        return parts[0] if len(parts) == 1 else ("alt", parts)
+
+    def cat(self):
+        parts = []
+        while self.peek() is not None and self.peek() not in "|)":
+            parts.append(self.repeat())
+        return ("cat", parts)
+
+    def number(self):
+        j = self.i
+        while self.peek() is not None and self.peek().isdigit():
+            self.i += 1
+        if j == self.i:
+            self.fail("a number is expected in {m,n}")
+        return int(self.p[j:self.i])
+
+    def repeat(self):
+        node = self.atom()
+        while self.peek() is not None and self.peek() in "*+?{":
+            ch = self.peek()
+            self.i += 1
+            if ch == "*":
+                node = ("rep", node, 0, None)
+            elif ch == "+":
+                node = ("rep", node, 1, None)
+            elif ch == "?":
+                node = ("rep", node, 0, 1)
+            else:
+                lo = hi = self.number()
+                if self.peek() == ",":
+                    self.i += 1
+                    hi = None if self.peek() == "}" else self.number()
+                if self.peek() != "}":
+                    self.fail("'}' is expected")
+                self.i += 1
+                if hi is not None and hi < lo:
+                    self.fail("{m,n} with n < m")
+                node = ("rep", node, lo, hi)
+        return node
+
+    def escape(self):
+        """The character after a backslash: a set."""
+        ch = self.peek()
+        if ch is None:
+            self.fail("a pattern cannot end in a backslash")
+        self.i += 1
+        if ch == "d":
+            return self.digits()
+        if ch.isalnum():
+            self.fail("unsupported escape \\%s" % ch)
+        return frozenset([self.cls(ch)])
+
+    def atom(self):
+        ch = self.peek()
+        if ch == "(":
+            self.i += 1
+            node = self.alt()
+            if self.peek() != ")":
+                self.fail("')' is expected")
+            self.i += 1
+            return node
+        if ch == "[":
+            self.i += 1
+            return ("set", self.bracket())
+        if ch in "*+?{":
+            self.fail("nothing to repeat")
+        self.i += 1
+        if ch == ".":
+            return ("set", frozenset(self.all))
+        if ch == "\\":
+            return ("set", self.escape())
+        if ch in "]}":
+            self.fail("unbalanced %r" % ch)
+        return ("set", frozenset([self.cls(ch)]))
+
+    def bracket(self):
+        negate = self.peek() == "^"
+        if negate:
+            self.i += 1
+        members, first = set(), True
+        while True:
+            ch = self.peek()
+            if ch is None:
+                self.fail("']' is expected")
+            if ch == "]" and not first:
+                self.i += 1
+                break
+            first = False
+            self.i += 1
+            if ch == "\\":
+                s = self.escape()
+                members |= s
+                continue
+            if self.peek() == "-" and self.i + 1 < len(self.p) and self.p[self.i + 1] != "]":
+                self.i += 1
+                hi = self.peek()
+                self.i += 1
+                if hi == "\\":
+                    hi = self.peek()
+                    self.i += 1
+                if ord(hi) < ord(ch):
+                    self.fail("bad range %s-%s" % (ch, hi))
+                self.cls(ch), self.cls(hi)                              # the ends must be symbols of the alphabet
+                for code in range(ord(ch), ord(hi) + 1):
+                    k = self.alphabet.char_to_idx.get(utf8_to_uxxxx(chr(code), output_array=True)[0])
+                    if k is not None and self.canon[k] != 0:
+                        members.add(self.canon[k])
+            else:
+                members.add(self.cls(ch))
+        return frozenset(self.all) - members if negate else frozenset(members)
+
+
+# ---- Thompson construction: tree -> NFA with epsilon moves
+class _Nfa(object):
+    def __init__(self):
+        self.eps, self.arcs = [], []                       # per state: epsilon targets; (set of classes, target)
+
+    def state(self):
+        self.eps.append([])
+        self.arcs.append([])
+        return len(self.eps) - 1
+
+    def build(self, node):
+        """(start, end) of a fresh fragment."""
+        kind = node[0]
+        if kind == "set":
+            a, b = self.state(), self.state()
+            if node[1]:
+                self.arcs[a].append((node[1], b))
+            return a, b
+        if kind == "cat":
+            a = b = self.state()
+            for part in node[1]:
+                c, d = self.build(part)
+                self.eps[b].append(c)
+                b = d
+            return a, b
+        if kind == "alt":
+            a, b = self.state(), self.state()
+            for part in node[1]:
+                c, d = self.build(part)
+                self.eps[a].append(c)
+                self.eps[d].append(b)
+            return a, b
+        _, inner, lo, hi = node
+        a = b = self.state()
+        for _ in range(lo):
+            c, d = self.build(inner)
+            self.eps[b].append(c)
+            b = d
+        if hi is None:                                     # inner*
+            c, d = self.build(inner)
+            e = self.state()
+            self.eps[b] += [c, e]
+            self.eps[d] += [c, e]
+            b = e
+        else:
+            e = self.state()
+            for _ in range(hi - lo):                       # (inner (inner ...)?)?
+                c, d = self.build(inner)
+                self.eps[b] += [c, e]
+                b = d
+            self.eps[b].append(e)
+            b = e
+        return a, b
+
+
+def _determinize(nfa, start, end):
+    """Subset construction.  (per state a dict class -> state, accept flags); state 0 is the start."""
+    closures = {}
+
+    def closure(states):
+        out = set()
+        for s in states:
+            if s not in closures:
+                seen, stack = {s}, [s]
+                while stack:
+                    for n in nfa.eps[stack.pop()]:
+                        if n not in seen:
+                            seen.add(n)
+                            stack.append(n)
+                closures[s] = frozenset(seen)
+            out |= closures[s]
+        return frozenset(out)
+
+    first = closure([start])
+    index, order, trans = {first: 0}, [first], []
+    k = 0
+    while k < len(order):
+        moves = {}
+        for n in order[k]:
+            for cset, tgt in nfa.arcs[n]:
+                for c in cset:
+                    moves.setdefault(c, set()).add(tgt)
+        row = {}
+        for c in sorted(moves):
+            nxt = closure(moves[c])
+            if nxt not in index:
+                index[nxt] = len(order)
+                order.append(nxt)
+            row[c] = index[nxt]
+        trans.append(row)
+        k += 1
+    return trans, [end in s for s in order]
+
+
+def _minimize(trans, accept):
+    """Trim (keep the states on a way from the start to an accepting state) and merge equivalent states.  State 0 stays the start;
+    states are numbered breadth first, classes ascending, so that equal languages give equal tables."""
+    n = len(trans)
+    reach, stack = {0}, [0]
+    while stack:
+        for d in trans[stack.pop()].values():
+            if d not in reach:
+                reach.add(d)
+                stack.append(d)
+    back = [[] for _ in range(n)]
+    for s in reach:
+        for d in trans[s].values():
+            back[d].append(s)
+    live = {s for s in reach if accept[s]}
+    stack = list(live)
+    while stack:
+        for s in back[stack.pop()]:
+            if s not in live:
+                live.add(s)
+                stack.append(s)
+    if 0 not in live:                                      # the empty language: the start state alone
+        return [{}], [False]
+    keep = sorted(live)
+    block = {s: int(bool(accept[s])) for s in keep}
+    count = len(set(block.values()))
+    while True:
+        sig = {s: (block[s], tuple(sorted((c, block[d]) for c, d in trans[s].items() if d in live))) for s in keep}
+        ids = {}
+        for s in keep:
+            ids.setdefault(sig[s], len(ids))
+        block = {s: ids[sig[s]] for s in keep}
+        if len(ids) == count:
+            break
+        count = len(ids)
+    rep = {}
+    for s in keep:
+        rep.setdefault(block[s], s)
+    number, order = {block[0]: 0}, [block[0]]
+    k = 0
+    while k < len(order):
+        s = rep[order[k]]
+        for c in sorted(trans[s]):
+            d = trans[s][c]
+            if d in live and block[d] not in number:
+                number[block[d]] = len(order)
+                order.append(block[d])
+        k += 1
+    out_t, out_a = [], []
+    for blk in order:
+        s = rep[blk]
+        out_t.append({c: number[block[d]] for c, d in trans[s].items() if d in live})
+        out_a.append(bool(accept[s]))
+    return out_t, out_a
+
+
+class Grammar(object):
+    """A minimised deterministic automaton over the alphabet's symbol classes: dead and unreachable states removed, state 0 the start,
+    the arcs in the kernel's order (dst, class, src).  Build one with from_regex, from_words, contains or from_dfa."""
+
+    def __init__(self, alphabet, trans, accept, name="grammar"):
+        self.alphabet, self.name = alphabet, name
+        self._canon = alphabet.canonical_indices()
+        self._trans, acc = _minimize(trans, accept)
+        self.accept = np.array(acc, dtype=np.int32)
+        arcs = sorted((d, c, s) for s, row in enumerate(self._trans) for c, d in row.items())
+        self.arc_dst = np.array([a[0] for a in arcs], dtype=np.int32)
+        self.arc_cls = np.array([a[1] for a in arcs], dtype=np.int32)
+        self.arc_src = np.array([a[2] for a in arcs], dtype=np.int32)
+
+    n_states = property(lambda self: len(self._trans))
+    n_arcs = property(lambda self: int(self.arc_dst.size))
+
+    @property
+    def max_in_degree(self):
+        return int(np.bincount(self.arc_dst, minlength=1).max()) if self.n_arcs else 0
+
+    def dfa(self):
+        """(per state a dict class -> state, accept flags): the tables from_dfa takes."""
+        return [dict(row) for row in self._trans], [bool(a) for a in self.accept]
+
+    def accepts(self, labels):
+        """Whether the automaton accepts a labelling: a utf-8 string or a sequence of alphabet indices."""
+        try:
+            seq = _labels(self.alphabet, self._canon, labels, "accepts")
+        except ValueError:
+            return False
+        s = 0
+        for c in seq:
+            s = self._trans[s].get(c)
+            if s is None:
+                return False
+        return bool(self.accept[s])
+
+    @classmethod
+    def from_regex(cls, alphabet, pattern):
+        """A WHOLE-LINE match of `pattern`: literals (utf-8; a symbol outside the alphabet is a ValueError), `.` (any symbol), `[abc]`,
+        `[a-z]`, `[^...]`, `\\d`, `\\` escapes of punctuation, `( )`, `|`, `*`, `+`, `?`, `{m}`, `{m,n}`, `{m,}`.  Thompson NFA, subset
+        construction, minimisation."""
+        tree = _Parser(alphabet, pattern).parse()
+        nfa = _Nfa()
+        start, end = nfa.build(tree)
+        trans, accept = _determinize(nfa, start, end)
+        return cls(alphabet, trans, accept, name="regex %r" % pattern)
+
+    @classmethod
+    def from_words(cls, alphabet, words):
+        """Accepts exactly the given words (utf-8 strings or index sequences): a trie, minimised."""
+        canon = alphabet.canonical_indices()
+        trans, accept = [{}], [False]
+        for w in words:
+            s = 0
+            for c in _labels(alphabet, canon, w, "from_words"):
+                if c not in trans[s]:
+                    trans[s][c] = len(trans)
+                    trans.append({})
+                    accept.append(False)
+                s = trans[s][c]
+            accept[s] = True
+        return cls(alphabet, trans, accept, name="a trie of %d words" % sum(accept))
+
+    @classmethod
+    def contains(cls, alphabet, keyword, whole_word=False):
+        """Accepts every line in which `keyword` occurs as a contiguous run of characters (.*keyword.*); with whole_word only where it
+        is bounded on both sides by a space (u0020) or by the line's ends."""
+        canon, every = _classes(alphabet)
+        lab = _labels(alphabet, canon, keyword, "contains")
+        if not lab:
+            raise ValueError("contains: empty keyword")
+        any_star = ("rep", ("set", frozenset(every)), 0, None)
+        word = [("set", frozenset([c])) for c in lab]
+        if whole_word:
+            sp = alphabet.char_to_idx.get("u0020")
+            if sp is None:
+                raise ValueError("contains(whole_word=True): the alphabet has no u0020 (space)")
+            sp = ("set", frozenset([canon[sp]]))
+            tree = ("cat", [("rep", ("cat", [any_star, sp]), 0, 1)] + word + [("rep", ("cat", [sp, any_star]), 0, 1)])
+        else:
+            tree = ("cat", [any_star] + word + [any_star])
+        nfa = _Nfa()
+        start, end = nfa.build(tree)
+        trans, accept = _determinize(nfa, start, end)
+        return cls(alphabet, trans, accept, name="contains %r%s" % (keyword, " (whole word)" if whole_word else ""))
+
+    @classmethod
+    def from_dfa(cls, alphabet, transitions, accept):
+        """Explicit tables: `transitions[s]` a dict symbol -> state (a symbol is an alphabet index or one utf-8 character), `accept[s]`
+        flags, state 0 the start.  Two symbols of one class must lead to the same state."""
+        canon = alphabet.canonical_indices()
+        if len(transitions) != len(accept) or not len(accept):
+            raise ValueError("from_dfa: need one accept flag per state and at least one state")
+        trans = []
+        for s, row in enumerate(transitions):
+            out = {}
+            for sym, d in row.items():
+                c = _labels(alphabet, canon, sym if isinstance(sym, str) else [sym], "from_dfa")[0]
+                d = int(d)
+                if d < 0 or d >= len(accept):
+                    raise ValueError("from_dfa: state %d has an arc to %d, outside 0 .. %d" % (s, d, len(accept) - 1))
+                if out.setdefault(c, d) != d:
+                    raise ValueError("from_dfa: state %d is not deterministic on class %d" % (s, c))
+            trans.append(out)
+        return cls(alphabet, trans, list(accept), name="dfa of %d states" % len(accept))
+
+
+def pack_grammars(grammars, device):
+    """The concatenated tables ops.ctc_grammar_scores takes, on `device`."""
+    s_off = np.cumsum([0] + [g.n_states for g in grammars]).astype(np.int32)
+    a_off = np.cumsum([0] + [g.n_arcs for g in grammars]).astype(np.int32)
+
+    def cat(name):
+        return torch.from_numpy(np.concatenate([getattr(g, name) for g in grammars]).astype(np.int32)).to(device)
+
+    return {"state_off": torch.from_numpy(s_off).to(device), "arc_off": torch.from_numpy(a_off).to(device), "src": cat("arc_src"),
+            "cls": cat("arc_cls"), "dst": cat("arc_dst"), "accept": cat("accept"),
+            "max_states": max(g.n_states for g in grammars), "max_arcs": max(g.n_arcs for g in grammars)}
+
+
+def group_grammars(grammars, T, B, want_best):
+    """`grammars` cut, in order, into the fewest consecutive groups that one vocr_ctc_grammar_scores call each can take: the largest state
+    count plus the largest arc count of a group within the kernel's cells (the two maxima may come from different grammars), and with
+    best paths T * B * group size * that sum * 4 bytes of back pointers within 2 GiB.  A grammar that does not fit a call of its own
+    is a ValueError that names it and its sizes."""
+    def fits(ms, ma, n):
+        return ms + ma <= ops.GRAMMAR_CELLS_MAX and (not want_best or T * B * n * (ms + ma) * 4 <= ops.GRAMMAR_BP_MAX_BYTES)
+
+    groups, ms, ma = [], 0, 0
+    for g in grammars:
+        if g.n_states + g.n_arcs > ops.GRAMMAR_CELLS_MAX:
+            raise ValueError("GrammarMatcher: %s has %d states + %d arcs, more than the kernel's %d cells (larger lexicons: "
+                             "WordBeamDecoder)" % (g.name, g.n_states, g.n_arcs, ops.GRAMMAR_CELLS_MAX))
+        if not fits(g.n_states, g.n_arcs, 1):
+            raise ValueError("GrammarMatcher: %s has %d states + %d arcs; its back pointers for %d frames x %d lines take %d bytes, more "
+                             "than %d: use fewer lines per call, or scores without best paths"
+                             % (g.name, g.n_states, g.n_arcs, T, B, T * B * (g.n_states + g.n_arcs) * 4, ops.GRAMMAR_BP_MAX_BYTES))
+        if groups and fits(max(ms, g.n_states), max(ma, g.n_arcs), len(groups[-1]) + 1):
+            groups[-1].append(g)
+            ms, ma = max(ms, g.n_states), max(ma, g.n_arcs)
+        else:
+            groups.append([g])
+            ms, ma = g.n_states, g.n_arcs
+    return groups
+
+
+class GrammarMatcher(object):
+    """Scores the model's output frames against grammars."""
+
+    def __init__(self, alphabet):
+        self.alphabet = alphabet
+        self._canon = {}
+
+    def canon(self, dev):
+        key = str(dev)
+        if key not in self._canon:
+            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        return self._canon[key]
+
+    def scores(self, model_output, lens, grammars, want_best=True):
+        """Device tensors (logp [B,G], best [B,G], labels [B,G,T], label_lens [B,G]); the last three None without want_best."""
+        grammars = list(grammars)
+        dev = model_output.device
+        T, B = int(model_output.shape[0]), int(model_output.shape[1])
+        groups = group_grammars(grammars, T, B, want_best)
+        outs =[ops.ctc_grammar_scores(model_output.detach(), lens, pack_grammars(grp, dev), self.canon(dev), want_best) for grp in groups]
+        if len(outs) == 1:
+            return outs[0]
+        return tuple(torch.cat([o[k] for o in outs], dim=1) if want_best or k == 0 else None for k in range(4))
+
+    def match(self, model_output, lens, grammars):
+        """`model_output` [T,B,V] logits on the device, `lens` the lines' frame counts, `grammars` a list of Grammar.  Returns
+        GrammarHits of host arrays from one device-to-host copy: logp [B,G] (natural log of the probability that the line's text is in
+        the language, -inf for 0), prob = exp(logp), best_logp [B,G] (the score of the best single path through the grammar), best_labels
+        [B][G] (its labelling as alphabet indices; None where nothing is accepted) and best_text [B][G] (the same as utf-8)."""
+        grammars = list(grammars)
+        B = int(model_output.shape[1])
+        if not grammars:
+            z = np.zeros((B, 0), dtype=np.float32)
+            return GrammarHits(z, z.astype(np.float64), z, [[] for _ in range(B)], [[] for _ in range(B)])
+        logp, best, labels, ln = self.scores(model_output, lens, grammars, True)
+        logp, best, labels, ln = one_copy([logp.unsqueeze(-1), best.unsqueeze(-1), labels, ln.unsqueeze(-1)])
+        logp, best, ln = logp[..., 0], best[..., 0], ln[..., 0]
+        idx_to_char = self.alphabet.idx_to_char
+        lab = [[None if ln[b, g] < 0 else [int(v) for v in labels[b, g, :ln[b, g]]] for g in range(len(grammars))] for b in range(B)]
+        text = [[None if l is None else uxxxx_to_utf8(" ".join(idx_to_char[v] for v in l)) for l in row] for row in lab]
+        return GrammarHits(logp, np.exp(logp.astype(np.float64)), best, lab, text)

@@ -5,7 +5,8 @@ WHAT THE NUMBER IS: for a line and a keyword, the EXPECTED NUMBER of times the k
 line's labelling, the expectation taken over ALL frame paths under the CTC model (exact: no beam, no hypothesis, no pruning).
 min(1, expected count) bounds the probability that the keyword occurs at all from above.  It is NOT that probability (two overlapping
 or repeated occurrences on one path count twice), no language model is involved, and characters are compared as the alphabet's symbol
-strings (indices with the same string are one character, as everywhere in this package)."""
+strings (indices with the same string are one character, as everywhere in this package).  The exact probability that a keyword occurs
+is KeywordSpotter.probability: the mass of the regular language .*keyword.* (vistaocr_amd/grammar.py, vocr_ctc_grammar_scores)."""
 import re
 from collections import namedtuple
 
@@ -72,6 +73,20 @@ class KeywordSpotter:
         for i, q in enumerate(qs):
             lab[i, :len(q)] = q
         return lab, np.array([len(q) for q in qs], dtype=np.int32), np.array(flags, dtype=np.int32), per
+
+    def probability(self, model_output, lens, keywords):
+        """The EXACT probability, under the CTC model, that each keyword occurs at least once in the line (with whole_word: bounded by
+        spaces or the line's ends): host array [B,Q], fp64.  The mass of the regular language .*keyword.* over all frame paths
+        (Grammar.contains through vocr_ctc_grammar_scores), next to search()'s expected count, which only bounds it from above.  No
+        language model is involved; one device-to-host copy."""
+        from .grammar import Grammar, GrammarMatcher
+        keywords = list(keywords)
+        B = int(model_output.shape[1])
+        if not keywords:
+            return np.zeros((B, 0), dtype=np.float64)
+        grammars = [Grammar.contains(self.alphabet, self.labels(k), whole_word=self.whole_word) for k in keywords]
+        logp = GrammarMatcher(self.alphabet).scores(model_output, lens, grammars, want_best=False)[0]
+        return np.exp(logp.cpu().numpy().astype(np.float64))
 
     def search(self, model_output, lens, keywords):
         """`model_output` [T,B,V] logits on the device, `lens` the lines' frame counts, `keywords` a list (forms: labels()).  Returns

@@ -1535,6 +1535,68 @@ def ctc_keyword_scores(logits, lens, queries, query_lens, query_flags=None, cano
     return log_count, best, span
 
 
+GRAMMAR_CELLS_MAX = 8192
+GRAMMAR_BP_MAX_BYTES = 1 << 31
+
+
+def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True):
+    """CTC grammar search (vocr_ctc_grammar_scores) on raw logits [T,B,V]: for every (line, automaton) the natural log of the exact
+    probability that the line's collapsed labelling is accepted - the sum over all frame paths, no beam - and, with `want_best`, the
+    best single path through the product of the CTC topology and the automaton with its labelling.  `lens` as for ctc_align;
+    `grammars_packed` a dict of the G concatenated automata (grammar.pack_grammars builds it): int32 device tensors "state_off" [G+1],
+    "arc_off" [G+1], "src", "cls", "dst" [arcs] (local state numbers, every automaton's arcs sorted by (dst, class, src)), "accept"
+    [states], and the ints "max_states", "max_arcs" (bounds of one automaton's sizes); `canon` int32 [V] device tensor of the symbol
+    classes or None.  Returns, on the device, (logp fp32 [B,G]; best fp32 [B,G]; labels int32 [B,G,T]; label_lens int32 [B,G]), the last
+    three None without want_best (no max pass runs and no back pointers are allocated; logp has the same bits either way).  -inf / -inf /
+    length -1 where nothing is accepted and, for every line, for an automaton that breaks a rule.  No weights on arcs, no gradient; best
+    is the best PATH, not the most probable accepted labelling.  Shapes, dtypes and the kernel's limits are checked here; the CONTENTS of
+    the tables stay on the device and are not read back (that would cost a synchronise per call): the kernel validates every automaton
+    against "max_states" / "max_arcs" and its own rules, but state_off[-1] <= accept.numel() and arc_off[-1] <= src.numel() are trusted,
+    as the header says - an offset beyond its array reads out of bounds.  grammar.pack_grammars always packs them consistently."""
+    gp = grammars_packed
+    names = ("state_off", "arc_off", "src", "cls", "dst", "accept")
+    _need_gpu(logits, *[gp[k] for k in names])
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    dev = logits.device
+    for k in names:
+        if gp[k].dtype != torch.int32 or gp[k].dim() != 1:
+            raise RuntimeError("ctc_grammar_scores: grammars_packed[%r] must be a 1-d int32 tensor" % k)
+    G = int(gp["state_off"].numel()) - 1
+    if G < 1 or gp["arc_off"].numel() != G + 1 or not (gp["src"].numel() == gp["cls"].numel() == gp["dst"].numel()):
+        raise RuntimeError("ctc_grammar_scores: need state_off and arc_off of G + 1 >= 2 entries and src, cls, dst of one length "
+                           "(state_off %d, arc_off %d, src %d, cls %d, dst %d)" % (gp["state_off"].numel(), gp["arc_off"].numel(),
+                                                                                  gp["src"].numel(), gp["cls"].numel(), gp["dst"].numel()))
+    ms, ma = int(gp["max_states"]), int(gp["max_arcs"])
+    nbytes = _lib.load().vocr_ctc_grammar_workspace_bytes(T, B, V, G, ms, ma, 1 if want_best else 0)
+    if nbytes == 0:
+        raise RuntimeError("ctc_grammar_scores: unsupported shape (T=%d B=%d V=%d G=%d max_states=%d max_arcs=%d; 2 <= V <= 256, "
+                           "max_states >= 1, max_states + max_arcs <= %d, T * B * G < 2^31, with best paths T * B * G * (max_states + "
+                           "max_arcs) * 4 bytes of back pointers <= 2 GiB)" % (T, B, V, G, ms, ma, GRAMMAR_CELLS_MAX))
+    if torch.is_tensor(lens):
+        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    if lens_dev.numel() != B:
+        raise RuntimeError("ctc_grammar_scores: %d lengths for %d lines" % (lens_dev.numel(), B))
+    if canon is not None:
+        _need_gpu(canon)
+        if canon.dtype != torch.int32 or canon.numel() != V:
+            raise RuntimeError("ctc_grammar_scores: canon must be int32 [V]")
+    t = {k: gp[k].contiguous() for k in names}
+    logp = torch.empty(B, G, dtype=torch.float32, device=dev)
+    best = labels = out_lens = None
+    if want_best:
+        best = torch.empty(B, G, dtype=torch.float32, device=dev)
+        labels = torch.empty(B, G, T, dtype=torch.int32, device=dev)
+        out_lens = torch.empty(B, G, dtype=torch.int32, device=dev)
+    ws = _ws(nbytes, dev)
+    call("vocr_ctc_grammar_scores", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G, _p(t["src"]),
+         _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(logp), _p(best), _p(labels), _p(out_lens), T, _p(ws), ws.numel() * 4,
+         _stream())
+    return logp, best, labels, out_lens
+
+
 EDIT_CHARS, EDIT_WORDS, EDIT_TRACE = 1, 2, 4
 EDIT_LEN_MAX = 2048
 EDIT_FIELDS = ("char_dist", "char_sub", "char_ins", "char_del", "hyp_chars", "ref_chars",
