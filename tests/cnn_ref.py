@@ -1,6 +1,6 @@
 """An fp64 restatement of the CNN ops of include/vocr.h (3x3 / pad-1 conv forward, data, weight and bias gradient; BatchNorm2d training
 and eval statistics, BatchNorm + ReLU apply and backward; FractionalMaxPool2d 2x2; ReLU + MaxPool2d(2,2)), the yardstick of
-tests/test_cnn_fp64_gpu.py.  Plain torch, on the device of its inputs: a conv is an F.unfold plus a float64 matmul, image by image, so
+tests/test_cnn_fp64_gpu.py and tests/test_cnn_seams_gpu.py.  Plain torch, on the device of its inputs: a conv is an F.unfold plus a float64 matmul, image by image, so
 the same code serves the CPU test and the GPU test (where torch has no float64 convolution of its own to lean on).
 
 The bars are fixed constants with their reasoning below; none is derived from a kernel's output.  tests/test_cnn_ref_cpu.py holds them
@@ -71,6 +71,50 @@ def conv3x3_wgrad(x, dy, absolute=False):
 
 def conv_bar(family, s):
     return CONV_C[family] * U * s
+
+
+# ---- minimal filtering at a tiny K.  The constants above measure a kernel's error against s, the products IN an output's support.  A
+# minimal-filtering kernel forms each output from transformed points of a whole tile - F(m,3): the m + 2 input columns of the output's
+# column group; the row-pair weight gradient: the 2 x 2 gradient pixels and 4 x 4 inputs of a block - and the tile's other values cancel
+# only in exact arithmetic: its rounding error scales with the tile, |e| <~ c U (largest tap of the filter row) (sum of |x| over the tile).
+# Summed over many products the two scales agree within a small factor (what x2 / x8 above stand for); an output that sums fewer
+# products than ONE K step of the kernels (a half-chunk of 4 input channels x 9 taps = 36) can have a support of small values beside
+# large neighbours, and an honest fp32 transform then misses C U s (tests/test_cnn_ref_cpu.py: 7.6x at 1 x 1 x 1 x 32 -> 132, F(4,3)).
+# Below TINY_K the same constants therefore apply to the scale of the tile, s_win >= s elementwise.
+TINY_K = 36
+
+
+def _windows(t, size, step, dims=(3,)):
+    """sum of |t| over windows of `size` every `step` along dims (t already padded)"""
+    t = t.abs().double()
+    for d in dims:
+        t = t.unfold(d, size, step)
+    return t.sum(tuple(range(-len(dims), 0)))
+
+
+def conv3x3_window(x, w, bias, m):
+    """s_win of an F(m,3) row transform (m = 2, 4): sum over (ci, kh) of the largest |tap| of the filter row x the sum of |x| over the
+    m + 2 columns m t - 1 .. m t + m of the output's column group t, + |bias|"""
+    x, w = _f(x), _f(w)
+    n, cin, h, wd = x.shape
+    t = (wd + m - 1) // m
+    win = _windows(F.pad(x, (1, m * t + 1 - wd, 1, 1)), m + 2, m)                       # [n][ci][h + 2][t]
+    gmax = w.abs().amax(-1)                                                            # [co][ci][kh]
+    s = torch.zeros(n, w.shape[0], h, t, dtype=torch.float64, device=x.device)
+    for kh in range(3):
+        s += torch.einsum("mk,nkht->nmht", gmax[:, :, kh], win[:, :, kh:kh + h])
+    s = s.repeat_interleave(m, 3)[..., :wd]
+    return s if bias is None else s + _f(bias).abs().view(1, -1, 1, 1)
+
+
+def conv3x3_wgrad_window(x, dy):
+    """s_win of the row-pair weight gradient: per (co, ci), the sum over blocks of (sum of |dy| over the block's 2 x 2 pixels) x (sum of
+    |x| over its 4 x 4 inputs, rows 2r - 1 .. 2r + 2 and columns 2p - 1 .. 2p + 2); the same for all nine taps"""
+    n, cin, h, wd = x.shape
+    h2, w2 = (h + 1) // 2, (wd + 1) // 2
+    xs = _windows(F.pad(_f(x), (1, 2 * w2 + 1 - wd, 1, 2 * h2 + 1 - h)), 4, 2, (2, 3))
+    ds = _windows(F.pad(_f(dy), (0, 2 * w2 - wd, 0, 2 * h2 - h)), 2, 2, (2, 3))
+    return torch.einsum("nohw,nihw->oi", ds, xs)[:, :, None, None].expand(-1, -1, 3, 3)
 
 
 def ratio(got, ref, bar):
@@ -248,28 +292,124 @@ def relu_maxpool2(x):
 
 
 # --------------------------------------------------------------------------------------------------------------------------- mutants
-MUTANTS = ("tap", "last4_cin", "tail_piece", "wgrad_slab", "last_vec", "biased_rv", "eps_out", "fp64_windows")
+MUTANTS = ("tap", "last4_cin", "tail_piece", "wgrad_slab", "last_vec", "biased_rv", "eps_out", "fp64_windows",
+           # the seam errors of tests/cnn_cases.py's tables (tests/test_cnn_seams_gpu.py)
+           "odd_last_col", "gap_slot", "cin_mod4", "pair_lower_row", "last_slab", "f16_pad")
+SEAM_CONV_MUTANTS = ("odd_last_col", "gap_slot", "cin_mod4")
+SEAM_WGRAD_MUTANTS = ("pair_lower_row", "last_slab", "f16_pad")
+
+
+def _next_row_first_col(x):
+    """[n][c][h]: for every row of the (n, h) stream of a channel, column 0 of the row that follows it in memory (the last row of an image
+    is followed by the first of the next image, the last image by zeros)"""
+    n, c, h, _ = x.shape
+    col = x[:, :, :, 0].transpose(0, 1).reshape(c, n * h)
+    nxt = torch.cat([col[:, 1:], torch.zeros(c, 1, dtype=x.dtype)], 1)
+    return nxt.view(c, n, h).transpose(0, 1)
 
 
 def conv_mutant(x, w, bias, mutant):
     """an fp32 conv (CPU) that is wrong on purpose: "tap" drops tap (1, 2) of the pair (co, ci) = (1, 2); "last4_cin" drops the last 4
-    input channels; "tail_piece" zeroes one tail piece (32 output channels x 8 pixels at the end of the last image's last row)."""
+    input channels; "tail_piece" zeroes one tail piece (32 output channels x 8 pixels at the end of the last image's last row).
+    The seams: "odd_last_col" leaves out the last column of a row of odd width (the half-filled last column group); "gap_slot" lets the
+    column right of a row's last one - the zero padding the gap slot of the slot stream stands for - read the first column of the next
+    row of the stream; "cin_mod4" drops the last Cin % 4 input channels (the partial half-chunk)."""
     w = w.clone()
     if mutant == "tap":
         w[1, 2, 1, 2] = 0
     elif mutant == "last4_cin":
         w[:, -4:] = 0
-    y = F.conv2d(x.float(), w.float(), None if bias is None else bias.float(), padding=1)
+    elif mutant == "cin_mod4" and w.shape[1] % 4:
+        w[:, -(w.shape[1] % 4):] = 0
+    b = None if bias is None else bias.float()
+    if mutant == "gap_slot":
+        xp = F.pad(x.float(), (1, 1, 1, 1))
+        xp[:, :, 1:-1, -1] = _next_row_first_col(x.float())
+        return F.conv2d(xp, w.float(), b)
+    y = F.conv2d(x.float(), w.float(), b, padding=1)
     if mutant == "tail_piece":
         y[-1, :32, -1, -8:] = 0
+    elif mutant == "odd_last_col" and x.shape[3] % 2:
+        y[..., -1] = 0 if b is None else b.view(1, -1, 1)
     return y
 
 
-def wgrad_mutant(x, dy, slabs=16):
-    """an fp32 weight gradient with one of `slabs` split slabs (a run of rows of the (n, h) stream) dropped: the last one."""
-    n, _, h, _ = x.shape
+def wgrad_mutant(x, dy, slabs=16, mutant="wgrad_slab"):
+    """an fp32 weight gradient that is wrong on purpose.  "wgrad_slab": one of `slabs` split slabs (a run of rows of the (n, h) stream)
+    dropped, the last one; "last_slab": the same at a kernel's own split count - `slabs` may exceed the rows, at least one row goes;
+    "pair_lower_row": with an odd H the lower row of every image's last row pair, which lies outside the image, is counted - it reads
+    the first row of what follows in memory (the next image; the first image after the last); "f16_pad": the first padded element of
+    the first row of the channel-major fp16 copy of x (vocr_f32_to_f16_layouts: the right halo of that row) holds 1 instead of 0."""
+    n, cin, h, wd = x.shape
+    x, dy = x.float(), dy.float()
+    shape = (dy.shape[1], cin, 3, 3)
+    if mutant == "pair_lower_row":
+        if h % 2 == 0:
+            return torch.nn.grad.conv2d_weight(x, shape, dy, padding=1)
+        below = lambda t: torch.cat([t, torch.roll(t, -1, 0)[:, :, :1]], 2)
+        return torch.nn.grad.conv2d_weight(below(x), shape, below(dy), padding=1)
+    if mutant == "f16_pad":
+        xe, dye = F.pad(x, (0, 1)), F.pad(dy, (0, 1))
+        xe[0, 0, 0, wd] = 1.0
+        return torch.nn.grad.conv2d_weight(xe, shape, dye, padding=1)
     rows = n * h
-    cut = rows - rows // slabs
+    cut = rows - (max(1, rows // slabs) if mutant == "last_slab" else rows // slabs)
     keep = torch.zeros(n, 1, h, 1)
     keep.view(-1)[:cut] = 1
-    return torch.nn.grad.conv2d_weight(x.float(), (dy.shape[1], x.shape[1], 3, 3), (dy * keep).float(), padding=1)
+    return torch.nn.grad.conv2d_weight(x, shape, dy * keep, padding=1)
+
+
+# ------------------------------------------------------------------------------------- honest fp32 minimal filtering (CPU, for the bars)
+_BT4 = ((4, 0, -5, 0, 1, 0), (0, -4, -4, 1, 1, 0), (0, 4, -4, -1, 1, 0), (0, -2, -1, 2, 1, 0), (0, 2, -1, -2, 1, 0), (0, 4, 0, -5, 0, 1))
+_G4 = ((1 / 4, 0, 0), (-1 / 6, -1 / 6, -1 / 6), (-1 / 6, 1 / 6, -1 / 6), (1 / 24, 1 / 12, 1 / 6), (1 / 24, -1 / 12, 1 / 6), (0, 0, 1))
+_AT4 = ((1, 1, 1, 1, 1, 0), (0, 1, -1, 2, -2, 0), (0, 1, 1, 4, 4, 0), (0, 1, -1, 8, -8, 1))
+_BT2 = ((1, 0, -1, 0), (0, 1, 1, 0), (0, -1, 1, 0), (0, 1, 0, -1))
+_G2 = ((1, 0, 0), (.5, .5, .5), (.5, -.5, .5), (0, 0, 1))
+_AT2 = ((1, 1, 1, 0), (0, 1, -1, -1))
+_WA = ((1, 0), (.5, .5), (.5, -.5), (0, 1))                 # weight gradient F(3,2): the gradient pair's four points
+_WBT = ((1, 0, -1, 0), (0, 1, 1, 0), (0, -1, 1, 0), (0, -1, 0, 1))
+_WGT = ((1, 1, 1, 0), (0, 1, -1, 0), (0, 1, 1, 1))
+
+
+def _mv(mat, v):
+    """rows of `mat` applied along the last dim of v, term by term in v's precision"""
+    out = []
+    for row in mat:
+        acc = None
+        for c, val in zip(row, v.unbind(-1)):
+            if c:
+                acc = val * c if acc is None else acc + val * c
+        out.append(acc)
+    return torch.stack(out, -1)
+
+
+def _mv2(mat, v):
+    """`mat` along the last two dims of v"""
+    return _mv(mat, _mv(mat, v).transpose(-1, -2)).transpose(-1, -2)
+
+
+def wino_conv_fp32(x, w, bias, m):
+    """the 3x3 convolution by F(m,3) along the row (m = 2, 4; points 0, +-1, (+-2,) infinity) in plain fp32 on the CPU: what an honest
+    minimal-filtering kernel computes, in one of its possible orders"""
+    bt, g, at = (_BT4, _G4, _AT4) if m == 4 else (_BT2, _G2, _AT2)
+    x, w = x.float(), w.float()
+    n, cin, h, wd = x.shape
+    t = (wd + m - 1) // m
+    v = _mv(bt, F.pad(x, (1, m * t + 1 - wd, 1, 1)).unfold(3, m + 2, m))                # [n][ci][h + 2][t][points]
+    u = _mv(g, w)                                                                      # [co][ci][kh][points]
+    acc = torch.zeros(n, w.shape[0], h, t, len(bt))
+    for ci in range(cin):
+        for kh in range(3):
+            acc = acc + u[None, :, ci, kh, None, None, :] * v[:, None, ci, kh:kh + h]
+    y = _mv(at, acc).reshape(n, w.shape[0], h, t * m)[..., :wd]
+    return y if bias is None else y + bias.float().view(1, -1, 1, 1)
+
+
+def wgrad_rowpair_fp32(x, dy):
+    """the weight gradient by F(3,2) along the row and across row pairs, in plain fp32 on the CPU"""
+    x, dy = x.float(), dy.float()
+    n, cin, h, wd = x.shape
+    h2, w2 = (h + 1) // 2, (wd + 1) // 2
+    xt = F.pad(x, (1, 2 * w2 + 1 - wd, 1, 2 * h2 + 1 - h)).unfold(2, 4, 2).unfold(3, 4, 2)
+    dt = F.pad(dy, (0, 2 * w2 - wd, 0, 2 * h2 - h)).unfold(2, 2, 2).unfold(3, 2, 2)
+    return _mv2(_WGT, torch.einsum("nohwrc,nihwrc->oirc", _mv2(_WA, dt), _mv2(_WBT, xt)))

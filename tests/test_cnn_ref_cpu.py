@@ -1,12 +1,15 @@
 """CPU: the CNN restatement of tests/cnn_ref.py against torch's float64 modules (conv2d and its gradients, batch_norm with running
 statistics) and ATen's fp32 fractional_max_pool2d indices; the bars of tests/test_cnn_fp64_gpu.py against computations that are wrong
-on purpose (every mutant misses its bar by at least 10x), and fp32 CPU results that must pass them."""
+on purpose (every mutant misses its bar by at least 10x), and fp32 CPU results that must pass them.  The same two questions for the seam
+tables of tests/cnn_cases.py (tests/test_cnn_seams_gpu.py): an honest fp32 convolution holds the bars on every small shape, each seam
+mutant misses its bar by 10x on at least one."""
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import cnn_cases as cc
 from tests import cnn_ref as cr
 
 
@@ -224,3 +227,158 @@ def test_fp64_windows_differ_from_the_fp32_rule():
         for u in rng.uniform(0, 1, size=300).astype(np.float32):
             diff += int((cr.fracpool_starts(u, in_size, out_size) != cr.fracpool_starts(u, in_size, out_size, np.float64)).any())
     assert diff > 0
+
+
+# ------------------------------------------------------------------------------------------- the seam tables of tests/cnn_cases.py
+_TABLES = [("WINO", cc.WINO_CASES, cc.WINO_AXES), ("DIRECT", cc.DIRECT_CASES, cc.DIRECT_AXES), ("H16", cc.H16_CASES, cc.H16_AXES),
+           ("F16", cc.F16_CASES, cc.F16_AXES), ("WGRAD_F16", cc.WGRAD_F16_CASES, cc.WGRAD_F16_AXES)]
+
+
+def test_the_seam_tables_are_short_and_cover_their_axes():
+    for name, rows, axes in _TABLES:
+        assert cc.covers2(rows, axes), name
+        assert len(rows) <= 4 * max(len(v) for v in axes.values()), (name, len(rows))          # a cross product has hundreds
+        assert len(set(rows)) == len(rows), name
+    for rows, cap in ((cc.WINO_CASES, cc.SMALL_CAP), (cc.DIRECT_CASES, cc.SMALL_CAP), (cc.H16_CASES, cc.H16_CAP), (cc.F16_CASES, cc.H16_CAP)):
+        assert max(n * cout * h * w for n, _, h, w, cout in rows) <= cap
+    assert all(cout % 4 == 0 for *_, cout in cc.WINO_CASES) and all(cout % 4 for *_, cout in cc.DIRECT_CASES)
+    assert cc.covers2([(n, h, w, (ci, co)) for n, ci, h, w, co in cc.WGRAD_CASES], cc.WGRAD_AXES)
+    assert cc.covers2([((n, h), w, (ci, co)) for n, ci, h, w, co in cc.WGRAD_H16_CASES], cc.WGRAD_H16_AXES)
+    assert cc.covers2(cc.LAYOUT_CASES, cc.LAYOUT_AXES)
+    # the large-grid plans: one shape per W % 4, Cin = 8, outputs of 25 M elements
+    assert set(cc.PLAN_CASES) | {1, 3, 4} == cc.REACHABLE_PLANS
+    for plan, shapes in cc.PLAN_CASES.items():
+        assert sorted(s[3] % 4 for s in shapes) == [0, 1, 2, 3] and all(s[1] == 8 for s in shapes), plan
+        assert max(n * co * h * w for n, _, h, w, co in shapes) < 25.1e6
+    # the weight-gradient table reaches all four kernels, an odd and an even H in each, and both reduce forms of the row-pair kernel
+    kinds = {}
+    for n, ci, h, w, co in cc.WGRAD_CASES:
+        kinds.setdefault(cc.wgrad_kernel(ci, co)[0], set()).add(h % 2)
+    assert kinds == {k: {0, 1} for k in ("rowpair", "wino3", "direct", "c1")}, kinds
+    wide = [3 * ci * co // 4 < 4096 and cc.rowpair_splits(n, ci, h, w, co) >= 64 for n, ci, h, w, co in cc.WGRAD_CASES
+            if cc.wgrad_kernel(ci, co)[0] == "rowpair"]
+    assert any(wide) and not all(wide)
+
+
+def _ops(shape, seed, f16=False):
+    """fp32-representable operands of a launch (n, K, h, w, M) as float64: x [n][K], the forward filter [M][K] and its bias, the
+    data-gradient layer's filter [K][M] (a layer M -> K whose gradient dy [n][K] gives dx [n][M]), dy for the weight gradient [n][M]"""
+    n, k, h, w, m = shape
+    r = lambda sh, i, sc=1.0: (cc.rand(sh, seed + i, sc).half() if f16 else cc.rand(sh, seed + i, sc)).double()
+    return r((n, k, h, w), 1), r((m, k, 3, 3), 2, 0.2), cc.rand((m,), seed + 3).double(), r((k, m, 3, 3), 4, 0.2), r((n, m, h, w), 5)
+
+
+def _honest(shape, seed, f16=False):
+    """error / the direct bar (the tightest) of torch's fp32 CPU forward, data gradient and weight gradient at a launch shape"""
+    x, wt, b, wd, dy = _ops(shape, seed, f16)
+    n, k, h, w, m = shape
+    y = F.conv2d(x.float(), wt.float(), b.float(), padding=1)
+    dx = torch.nn.grad.conv2d_input((n, m, h, w), wd.float(), x.float(), padding=1)
+    dw = torch.nn.grad.conv2d_weight(x.float(), wt.shape, dy.float(), padding=1)
+    return (cr.ratio(y, cr.conv3x3(x, wt, b), cr.conv_bar("direct", cr.conv3x3(x, wt, b, absolute=True))),
+            cr.ratio(dx, cr.conv3x3_dgrad(x, wd), cr.conv_bar("direct", cr.conv3x3_dgrad(x, wd, absolute=True))),
+            cr.ratio(dw, cr.conv3x3_wgrad(x, dy), cr.conv_bar("direct", cr.conv3x3_wgrad(x, dy, absolute=True))))
+
+
+@pytest.mark.parametrize("table", ["WINO", "DIRECT", "WGRAD", "H16", "F16", "WGRAD_F16", "WGRAD_H16"])
+def test_an_honest_fp32_conv_holds_the_bars_on_every_small_seam_shape(table):
+    """the condition that the tables are fair to a correct kernel: plain fp32 arithmetic, in torch's CPU order, stays within the
+    tightest bar (8 U s) at every small shape - on the fp16-rounded operands for the fp16 tables, as the GPU test compares"""
+    rows = cc.WGRAD_CASES if table == "WGRAD" else cc.WGRAD_H16_CASES if table == "WGRAD_H16" else dict((t[0], t[1]) for t in _TABLES)[table]
+    worst = 0.0
+    for i, shape in enumerate(rows):
+        r = max(_honest(shape, 100 * i, f16="16" in table))
+        assert r <= 1.0, (table, shape, r)
+        worst = max(worst, r)
+    print("%s: %d shapes, worst error / bar %.3f" % (table, len(rows), worst))
+
+
+@pytest.mark.parametrize("mutant", cr.SEAM_CONV_MUTANTS)
+def test_the_conv_bars_reject_the_seam_mutants(mutant):
+    """against the LOOSEST conv bar (F(4,3): 64 U s), on the shapes of the forward table the mutant applies to"""
+    hit, tried = [], 0
+    for i, shape in enumerate(cc.WINO_CASES + cc.DIRECT_CASES):
+        n, k, h, w, m = shape
+        if (mutant == "odd_last_col" and w % 2 == 0) or (mutant == "cin_mod4" and k % 4 == 0) or (mutant == "gap_slot" and n * h == 1):
+            continue
+        x, wt, b, _, _ = _ops(shape, 100 * i)
+        r = cr.ratio(cr.conv_mutant(x, wt, b, mutant), cr.conv3x3(x, wt, b), max(cr.CONV_C.values()) * cr.U * cr.conv3x3(x, wt, b, absolute=True))
+        tried += 1
+        hit.append(r >= 10.0)
+    print("%s: rejected by 10x on %d of %d shapes" % (mutant, sum(hit), tried))
+    assert tried >= 10 and all(hit), (mutant, sum(hit), tried)
+
+
+@pytest.mark.parametrize("mutant", cr.SEAM_WGRAD_MUTANTS)
+def test_the_wgrad_bars_reject_the_seam_mutants(mutant):
+    """pair_lower_row / last_slab against the row-pair kernel's bar (16 U s) on the weight-gradient table (last_slab at the kernel's own
+    split count); f16_pad against the fp16 bar (8 U s) on the fp16 weight-gradient table, fp16-rounded operands"""
+    hit, tried = [], 0
+    f16 = mutant == "f16_pad"
+    for i, shape in enumerate(cc.WGRAD_H16_CASES if f16 else cc.WGRAD_CASES):
+        n, k, h, w, m = shape
+        if not f16 and cc.wgrad_kernel(k, m)[0] != "rowpair":
+            continue
+        if (mutant == "pair_lower_row" and h % 2 == 0) or (mutant == "last_slab" and cc.rowpair_splits(*shape) == 1):
+            continue
+        x, _, _, _, dy = _ops(shape, 100 * i, f16)
+        got = cr.wgrad_mutant(x, dy, slabs=cc.rowpair_splits(*shape), mutant=mutant)
+        r = cr.ratio(got, cr.conv3x3_wgrad(x, dy), cr.conv_bar("f16" if f16 else "wgrad", cr.conv3x3_wgrad(x, dy, absolute=True)))
+        tried += 1
+        hit.append(r >= 10.0)
+    print("%s: rejected by 10x on %d of %d shapes" % (mutant, sum(hit), tried))
+    assert tried >= 3 and all(hit), (mutant, sum(hit), tried)
+
+
+def test_the_fp16_layout_restatement_pads_with_zeros():
+    x = cc.rand((2, 16, 3, 9), 5)
+    nhwc, nchwp = cc.f16_layouts_ref(x)
+    assert nchwp.shape[-1] == cc.padded_row(9) == 24 and cc.padded_row(8) == 16 and cc.padded_row(1) == 16
+    assert torch.equal(nchwp[..., :9], x.half()) and float(nchwp[..., 9:].abs().max()) == 0.0
+    assert torch.equal(nhwc[1, 0, 2, 4], x.half()[1, :16, 2, 4])
+    assert cc.f16_layouts_ref(x[:, :8])[0] is None
+
+
+def test_minimal_filtering_at_a_tiny_k_is_held_to_the_scale_of_its_tile():
+    """an honest fp32 F(m,3) convolution and row-pair weight gradient (cnn_ref.wino_conv_fp32 / wgrad_rowpair_fp32) over the tables: within
+    the plain bar C U s wherever an output sums TINY_K products or more, within the bar of the tile (s_win) below - where they do miss
+    the plain bar, so a correct kernel cannot be held to it there.  The seam mutants still miss the tile's bar by 10x at those shapes."""
+    over, n_tiny = 0.0, 0
+    for dgrad in (False, True):
+        for i, shape in enumerate(cc.WINO_CASES):
+            n, k, h, w, m = shape
+            x, wt, b, wd, _ = _ops(shape, 7 * i)
+            g, b = (wd.transpose(0, 1).flip(2, 3), None) if dgrad else (wt, b)
+            mf, fam = (4, "f43") if m >= 64 else (2, "f23")
+            got, ref, s, sw = cr.wino_conv_fp32(x, g, b, mf), cr.conv3x3(x, g, b), cr.conv3x3(x, g, b, absolute=True), cr.conv3x3_window(x, g, b, mf)
+            assert bool((sw >= s * (1 - 1e-12)).all())
+            r = cr.ratio(got, ref, cr.conv_bar(fam, s))
+            if 9 * k >= cr.TINY_K:
+                assert r <= 1.0, (shape, dgrad, r)
+                continue
+            over, n_tiny = max(over, r), n_tiny + 1
+            assert cr.ratio(got, ref, cr.conv_bar(fam, sw)) <= 1.0, (shape, dgrad)
+            for mutant in cr.SEAM_CONV_MUTANTS:
+                if (mutant == "odd_last_col" and w % 2 == 0) or (mutant == "cin_mod4" and k % 4 == 0) or (mutant == "gap_slot" and n * h == 1):
+                    continue
+                assert cr.ratio(cr.conv_mutant(x, g, b, mutant), ref, cr.conv_bar(fam, sw)) >= 10.0, (shape, dgrad, mutant)
+    assert n_tiny >= 10 and over > 1.0, (n_tiny, over)
+    print("F(m,3) at K < %d: %d launches, honest fp32 up to %.2f of the plain bar" % (cr.TINY_K, n_tiny, over))
+    over, n_tiny = 0.0, 0
+    for i, shape in enumerate(cc.WGRAD_CASES):
+        n, k, h, w, m = shape
+        if cc.wgrad_kernel(k, m)[0] != "rowpair":
+            continue
+        x, _, _, _, dy = _ops(shape, 11 * i)
+        got, ref, s, sw = cr.wgrad_rowpair_fp32(x, dy), cr.conv3x3_wgrad(x, dy), cr.conv3x3_wgrad(x, dy, absolute=True), cr.conv3x3_wgrad_window(x, dy)
+        assert bool((sw >= s * (1 - 1e-12)).all())
+        r = cr.ratio(got, ref, cr.conv_bar("wgrad", s))
+        if n * h * w >= cr.TINY_K:
+            assert r <= 1.0, (shape, r)
+            continue
+        over, n_tiny = max(over, r), n_tiny + 1
+        assert cr.ratio(got, ref, cr.conv_bar("wgrad", sw)) <= 1.0, shape
+        if h % 2:
+            assert cr.ratio(cr.wgrad_mutant(x, dy, mutant="pair_lower_row"), ref, cr.conv_bar("wgrad", sw)) >= 10.0, shape
+    assert n_tiny >= 3 and over > 1.0, (n_tiny, over)
+    print("row-pair weight gradient below %d pixels: %d launches, honest fp32 up to %.2f of the plain bar" % (cr.TINY_K, n_tiny, over))
