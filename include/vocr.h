@@ -680,6 +680,57 @@ int vocr_edit_stats(const int32_t* a_labels, const int32_t* a_lens, int na, int 
                     int32_t* out_stats, int32_t* out_confusion, uint8_t* out_ops, int ops_stride,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- training augmentation of a collated batch: src/train_cnn_lstm.py:203-274 (--synth_input, --stripe), src/imagetransforms.py:71-406 ---- */
+/* y = the augmented batch.  x[b][c][h][wmax] fp32 in [0, 1] as the collater builds it and the model takes it, widths[b] device int32
+ * (clamped to [0, wmax]), c = 1 or 3; y has the same shape and must not be x or overlap it.  WIDTHS DO NOT CHANGE: every line keeps
+ * its own box [0, h) x [0, w), so the model's sorted widths, its length map and the packed LSTM rows are untouched; the reference's
+ * crop / pad jitter is therefore a mild zoom and shift INSIDE the box (part of A below), not a new width.  All randomness is drawn on
+ * the host and arrives in tables; the call is a pure function of its arguments, bit-identical from run to run (no floating-point
+ * atomics; the only reduction is a min / max).
+ * params[b][24] device 32-bit words, one record per line (f: fp32 bits, i: int32, u: uint32):
+ *    0..5  f  A = a00 a01 a02 a10 a11 a12, the INVERSE affine map from output pixel indices to source pixel indices:
+ *             xs = a00 px + a01 py + a02, ys = a10 px + a11 py + a12
+ *    6..10 f  block filter taps k00 k01 k10 k11 and bias
+ *   11     f  contrast factor alpha (exactly 1: the contrast step is skipped, so that an identity record is a bitwise identity)
+ *   12 13  f  noise probability per pixel, noise sigma            14 15  f  delete probability per pixel, delete value
+ *   16     f  stripe value
+ *   17     u  flags: bit 0 mesh warp, bit 1 block filter, bit 2 invert
+ *   18     i  gw, the line's number of mesh CELLS along x (clamped to [1, gw_max]); it has gw + 1 node columns
+ *   19 20  i  stripe rows [r0, r1) (empty when r0 >= r1)
+ *   21 22  u  the line's 64-bit noise key, low word first        23  reserved, 0
+ * mesh[b][2][gh + 1][gw_max + 1] fp32 (may be NULL: no line is warped and bit 0 is ignored): node displacements in pixels, plane 0
+ * along x, plane 1 along y, of a regular control grid of gh x gw cells spanning the line (WarpImage's grid with
+ * fit_interval_to_image: gw = max(1, round(w / interval)), gh likewise from h); node (i, j) sits at (j w / gw, i h / gh).
+ * Per output pixel (ch, oy, ox < w), in fp32, every multiply-add fused as written here:
+ *  1 geometry: px = ox, py = oy; with bit 0: u = px * (gw / w), v = py * (gh / h), j = min(floor u, gw - 1), i = min(floor v, gh - 1),
+ *    D = bilinear interpolation of the four nodes of cell (i, j) at (u - j, v - i), p += D.  (The reference interpolates the scattered
+ *    nodes with scipy's Delaunay griddata; here it is bilinear on the regular grid.)  Without bit 0, D is exactly 0.  (xs, ys) = A (p, 1),
+ *    xs clamped to [0, w - 1], ys to [0, h - 1] (border replicate, the rule of the reference's warpAffine call; a NaN becomes 0).
+ *    R(oy, ox) = bilinear sample of x[b][ch] at (xs, ys) with taps floor and min(floor + 1, limit), lerp(a, b, t) = fma(t, b - a, a):
+ *    no tap ever reads a column >= w, so the pad columns of x may hold anything, NaN included.  All channels share the geometry.
+ *  2 block filter (bit 1, TessBlockConv: a 2x2 convolution with zero padding 1 cropped to the top-left h x w):
+ *    F(oy, ox) = bias + sum_{i,j in {0,1}} k[i][j] R(oy - 1 + i, ox - 1 + j), R = 0 outside [0, h) x [0, w); then the reference's
+ *    renormalisation over the WHOLE line, all channels: v = (F - min) / (max - min), 0 when max = min (the reference divides by zero
+ *    there).  No quantisation to uint8.  Without bit 1, v = R.
+ *  3 photometric, in this order: contrast v = (v - 0.5) alpha + 0.5; invert (bit 2) v = 1 - v; noise: with probability p_noise
+ *    v += sigma n, n standard normal; delete: with probability p_del v = del_value; stripe: rows [r0, r1) = stripe_value; clamp to
+ *    [0, 1] (a NaN becomes 0).  The draws: bits(draw) = upper 32 bits of vocr_dropout_fwd's hash (the splitmix64 finaliser) of
+ *    key * 0x9e3779b97f4a7c15 + (ox | oy << 24 | ch << 48 | draw << 56): a function of the line's key and the pixel only, not of
+ *    wmax, b or the launch.  A uniform is (bits >> 8) * 2^-24, exactly representable, so the decisions u < p are exact.  draw 0: the
+ *    noise decision; n = sqrt(-2 ln u1) cos(2 pi u2) (Box-Muller in fp32), u1 = ((bits(1) >> 8) + 1) * 2^-24, u2 = (bits(2) >> 8) *
+ *    2^-24; draw 3: the delete decision.
+ *  4 padding: y[b][:][:][ox >= w] = 0, the collater's zero pad.
+ * with_filter = 0 promises that no record has bit 1 set: the min / max pass is not launched, bit 1 is ignored and workspace may be
+ * NULL.  Otherwise pass 1 writes one (min, max) per workgroup to the workspace (8-byte aligned, vocr_augment_workspace_bytes; 0 for
+ * an unsupported shape) and pass 2 folds them; min and max do not depend on the order.  WHAT IT IS NOT: no gradient, no change of
+ * width or batch order, no parity claim against OpenCV or imgaug; imgaug's Grayscale and Emboss are not built.  Limits: 1 <= b <=
+ * 65535, h, wmax <= 2^24.  Bad arguments (a null pointer, b, c, h or wmax < 1, c not 1 or 3, y = x, a workspace too small) fail with
+ * VOCR_EINVAL before any launch. */
+size_t vocr_augment_workspace_bytes(int b, int c, int h, int wmax);
+int vocr_augment_lines(const float* x, const int32_t* widths, int b, int c, int h, int wmax, const uint32_t* params,
+                       const float* mesh, int gh, int gw_max, int with_filter, float* y,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

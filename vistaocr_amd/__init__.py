@@ -21,7 +21,8 @@ from .lm import CharNgramLM, WordNgramLM                                        
 from .model import CnnOcrModel                                                          # noqa: F401,E402
 from .train import FlatClampAdam, make_optimizer, seed_rank, train, train_async                                    # noqa: F401,E402
 from .dataset import OcrDataset                                                         # noqa: F401,E402
+from .augment import AugmentParams, DeviceAugmenter                                     # noqa: F401,E402
 
-__all__ = ["Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "ArgmaxDecoder", "BeamDecoder",
+__all__ = ["DeviceAugmenter", "AugmentParams","Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "ArgmaxDecoder", "BeamDecoder",
            "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "Grammar", "GrammarMatcher", "GrammarHits", "ErrorScorer", "ErrorStats", "OracleStats",
            "CnnOcrModel", "FlatClampAdam", "make_optimizer", "seed_rank", "train", "train_async", "OcrDataset"]

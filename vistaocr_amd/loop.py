@@ -229,9 +229,11 @@ def save_snapshot(path, iteration, model, optimizer, rtl, cur_lr, val_loss, val_
 
 def fit(model, criterion, optimizer, train_dataloader, validation_dataloader, train_fn, snapshot_prefix, batch_size,
         n_epochs=1, snapshot_every_n_iterations=1000, patience=10, min_lr=1e-7, rtl=False, line_height=30,
-        validate_fn=test_on_val):
+        validate_fn=test_on_val, augmenter=None):
     """The loop of src/train_cnn_lstm.py:375-470: train, validate every N iterations, plateau schedule on val WER,
-    snapshot, copy to best, reload best after an LR drop, stop when the schedule is exhausted.  Returns a history dict."""
+    snapshot, copy to best, reload best after an LR drop, stop when the schedule is exhausted.  Returns a history dict.
+    `augmenter` (a vistaocr_amd.DeviceAugmenter, or any callable batch -> batch): applied to every TRAINING batch before `train_fn`
+    sees it, never to a validation batch; None (the default): the batches go to `train_fn` as the loader yields them."""
     snapshot_path = snapshot_prefix + "-cur_snapshot.pth"
     best_model_path = snapshot_prefix + "-best_model.pth"
     scheduler = ReduceLROnPlateau(optimizer, mode="min", patience=patience, min_lr=min_lr)
@@ -245,18 +247,20 @@ def fit(model, criterion, optimizer, train_dataloader, validation_dataloader, tr
     gc.freeze()
     try:
         return _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataloader, train_fn, snapshot_path, best_model_path,
-                         batch_size, n_epochs, snapshot_every_n_iterations, rtl, line_height, validate_fn, scheduler, lr_alpha, hist)
+                         batch_size, n_epochs, snapshot_every_n_iterations, rtl, line_height, validate_fn, scheduler, lr_alpha, hist, augmenter)
     finally:
         gc.unfreeze()       # the freeze is this call's, not the process's: a host that calls fit() again, or lives on, collects as before
 
 
 def _fit_loop(model, criterion, optimizer, train_dataloader, validation_dataloader, train_fn, snapshot_path, best_model_path, batch_size,
-              n_epochs, snapshot_every_n_iterations, rtl, line_height, validate_fn, scheduler, lr_alpha, hist):
+              n_epochs, snapshot_every_n_iterations, rtl, line_height, validate_fn, scheduler, lr_alpha, hist, augmenter=None):
     iteration = 0
     best_val_wer = float("inf")
     for _epoch in range(1, n_epochs + 1):
         for batch in train_dataloader:
             iteration += 1
+            if augmenter is not None:
+                batch = augmenter(batch)
             hist["loss"].append(train_fn(batch, model, criterion, optimizer) / batch_size)
             if iteration % snapshot_every_n_iterations != 0:
                 continue

@@ -1597,6 +1597,39 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
     return logp, best, labels, out_lens
 
 
+AUGMENT_REC_WORDS = 24
+
+
+def augment_lines(x, widths, params, mesh=None, gh=0, gw_max=0, with_filter=True):
+    """Training augmentation of a collated batch (vocr_augment_lines): y, a new tensor shaped like `x` [B, C, H, Wmax] (fp32 device
+    tensor in [0, 1], C = 1 or 3).  `widths` int32 [B], `params` int32 (or uint32 bits) [B * 24] and `mesh` fp32 [B * 2 * (gh + 1) *
+    (gw_max + 1)] or None are DEVICE tensors in the layout of include/vocr.h (augment.AugmentParams.packed builds them in one buffer);
+    every line keeps its width.  with_filter=False promises that no record has the block-filter flag: the min / max pass and its
+    workspace are skipped.  Shapes and dtypes are checked here; the CONTENTS of the tables stay on the device and are not read back -
+    the kernel clamps every index it derives from them, so a bad record gives a wrong picture, never an access outside x.  No gradient
+    flows through it."""
+    _need_gpu(x, widths, params, mesh)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise RuntimeError("augment_lines: x must be fp32 [B, C, H, Wmax]")
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    if widths.dtype != torch.int32 or widths.numel() != B or params.dtype != torch.int32 or params.numel() != B * AUGMENT_REC_WORDS:
+        raise RuntimeError("augment_lines: need int32 widths [B] and int32 params [B * %d] (B=%d, widths %d, params %d)"
+                           % (AUGMENT_REC_WORDS, B, widths.numel(), params.numel()))
+    if mesh is not None and (mesh.dtype != torch.float32 or gh < 1 or gw_max < 1 or mesh.numel() != B * 2 * (gh + 1) * (gw_max + 1)):
+        raise RuntimeError("augment_lines: mesh must be fp32 [B * 2 * (gh + 1) * (gw_max + 1)] with gh, gw_max >= 1")
+    widths, params = widths.contiguous(), params.contiguous()
+    mesh = mesh.contiguous() if mesh is not None else None
+    nbytes = _lib.load().vocr_augment_workspace_bytes(B, C, H, W)
+    if nbytes == 0:
+        raise RuntimeError("augment_lines: unsupported shape (B=%d C=%d H=%d Wmax=%d; C must be 1 or 3)" % (B, C, H, W))
+    y = torch.empty_like(x)
+    ws = _ws(nbytes, x.device) if with_filter else None
+    call("vocr_augment_lines", _p(x), _p(widths), B, C, H, W, _p(params), _p(mesh), int(gh), int(gw_max), 1 if with_filter else 0, _p(y),
+         _p(ws), ws.numel() * 4 if ws is not None else 0, _stream())
+    return y
+
+
 EDIT_CHARS, EDIT_WORDS, EDIT_TRACE = 1, 2, 4
 EDIT_LEN_MAX = 2048
 EDIT_FIELDS = ("char_dist", "char_sub", "char_ins", "char_del", "hyp_chars", "ref_chars",
