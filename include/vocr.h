@@ -731,6 +731,31 @@ int vocr_augment_lines(const float* x, const int32_t* widths, int b, int c, int 
                        const float* mesh, int gh, int gw_max, int with_filter, float* y,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- alignment entropy of a labelling and its gradient: entropy-regularised CTC training (EnCTC, Liu, Jin and Zhang 2018) ---- */
+/* For the ONE labelling of each line, with p(pi) = prod_t P_t(pi_t) over the frame paths pi that collapse to it:
+ *   out_ctc[B]     = ln P,  P = sum_pi p(pi)                  the same bits as vocr_ctc_nbest_grad's out_ctc, with or without coeff
+ *   out_entropy[B] = H = - sum_pi (p / P) ln (p / P) = N / P + ln P >= 0 (clamped at 0),   N = sum_pi p(pi) * (-ln p(pi))
+ * the entropy, in nats, of the posterior over the feasible alignments: 0 when one alignment holds all the mass, ln(number of feasible
+ * paths) on uniform logits.  With coeff[B][2] = (w_ctc, w_ent) (device fp32) given,
+ *   dlogits[T][B][V] = d/dlogits  sum_b ( w_ctc_b * ln P_b + w_ent_b * H_b )
+ *   dlogits[t][b][v] = p_t(v) / P_t(c) * ( w_ctc occ(t, c) + w_ent (occN(t, c) - (N / P) occ(t, c)) ) - p_t(v) w_ctc,    c = class(v),
+ * occ as in vocr_ctc_nbest_grad and occN(t, c) = (1 / P) * the sum of p * (-ln p) over the paths with pi_t = c.  Rows t >= lens[b] are
+ * zeros.  Inputs, classes, blank, transition rule, validity rules and the -inf places are vocr_ctc_nbest_grad's with n = 1 (labels
+ * [B][label_stride], label_lens [B]).  A labelling that cannot be scored gets out_ctc = -inf and out_entropy = 0 and contributes
+ * exactly nothing to dlogits (its rows are zeros); L = 0 has one path and H = 0.  -inf logits are legal and never yield NaN or inf.
+ * No floating-point atomics: every sum has a fixed order, results are bit-identical from run to run, and a line's rows depend on that
+ * line alone.  coeff == NULL (then dlogits must be NULL, and the other way round): scores only - the forward sweep alone, nothing
+ * stored.  Limits: 2 <= v <= 256, 0 <= max_label_len <= min(t, 1663) (the sweep keeps TWO rows in the LDS, the path sum's and the
+ * entropy's, where the other labelling entries keep one and reach 1823), label_stride >= max_label_len, t * b < 2^31, and with coeff the four lattices,
+ * b * 16 * t * (2 * max_label_len + 1) bytes, at most 2 GiB.  Workspace from vocr_ctc_entropy_workspace_bytes (0 for an unsupported
+ * shape) = the class log-probabilities (t * b * v * 4 bytes rounded up to 16), and with want_grad the
+ * lattices behind them.  Bad arguments and unsupported shapes fail with VOCR_EINVAL before any launch. */
+size_t vocr_ctc_entropy_workspace_bytes(int t, int b, int v, int max_label_len, int want_grad);
+int vocr_ctc_entropy(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                     const int32_t* labels, const int32_t* label_lens, int label_stride, int max_label_len,
+                     const float* coeff, float* out_ctc, float* out_entropy, float* dlogits,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
  * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */

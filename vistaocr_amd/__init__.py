@@ -16,6 +16,7 @@ from .grammar import Grammar, GrammarHits, GrammarMatcher                       
 from .score import ErrorScorer, ErrorStats, OracleStats                                  # noqa: F401,E402
 from .ctc import CTCLoss                                                                # noqa: F401,E402
 from .risk import MinErrorRateLoss                                                      # noqa: F401,E402
+from .entropy import EntropyRegularizedCTCLoss                                          # noqa: F401,E402
 from .decoder import ArgmaxDecoder, BeamDecoder, WordBeamDecoder                        # noqa: F401,E402
 from .lm import CharNgramLM, WordNgramLM                                                # noqa: F401,E402
 from .model import CnnOcrModel                                                          # noqa: F401,E402
@@ -23,6 +24,6 @@ from .train import FlatClampAdam, make_optimizer, seed_rank, train, train_async 
 from .dataset import OcrDataset                                                         # noqa: F401,E402
 from .augment import AugmentParams, DeviceAugmenter                                     # noqa: F401,E402
 
-__all__ = ["DeviceAugmenter", "AugmentParams","Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "ArgmaxDecoder", "BeamDecoder",
+__all__ = ["DeviceAugmenter", "AugmentParams","Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "EntropyRegularizedCTCLoss", "ArgmaxDecoder", "BeamDecoder",
            "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "Grammar", "GrammarMatcher", "GrammarHits", "ErrorScorer", "ErrorStats", "OracleStats",
            "CnnOcrModel", "FlatClampAdam", "make_optimizer", "seed_rank", "train", "train_async", "OcrDataset"]

@@ -127,6 +127,8 @@ SIGNATURES = {
     "vocr_edit_stats": (I, [P, P, I, I, I, P, P, I, I, I, P, I, P, P, I, I, P, P, P, I, P, Z, P]),
     "vocr_augment_workspace_bytes": (Z, [I, I, I, I]),
     "vocr_augment_lines": (I, [P, P, I, I, I, I, P, P, I, I, I, P, P, Z, P]),
+    "vocr_ctc_entropy_workspace_bytes": (Z, [I, I, I, I, I]),
+    "vocr_ctc_entropy": (I, [P, P, I, I, I, P, P, P, I, I, P, P, P, P, P, Z, P]),
     "vocr_clamp_adam": (I, [P, P, P, P, Z, F, F, F, F, F, F, F, I, P, P]),
     "vocr_clamp": (I, [P, Z, F, P, P]),
     "vocr_comm_unique_id": (I, [P]),

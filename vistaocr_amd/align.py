@@ -177,6 +177,23 @@ class CtcAligner:
                                            self.canon(dev), self.alphabet, topk)
         return [row[:len(h)] for row, h in zip(rows, hyps)] if nbest else [row[0] for row in rows]
 
+    def entropy(self, model_output, lens, labels):
+        """How far the spans of align() can be trusted: per line (ln P_ctc, H, H / len), H the entropy in nats of the posterior over
+        the transcript's feasible frame alignments (vocr_ctc_entropy, scores only) and len the line's frames.  H = 0: one alignment holds
+        all the mass and the Viterbi spans are the only reading; H / len near ln 2 or above: the frames are spread over many alignments
+        and a span is good to several frames at best.  `labels`: per line a list of alphabet indices or a string of space-joined uxxxx
+        tokens (no n-best lists).  A transcript without an alignment gives (-inf, 0.0, 0.0).  One device-to-host copy."""
+        hyps, nbest, lab, ln = self._pack(labels)
+        if nbest:
+            raise ValueError("CtcAligner.entropy takes one transcript per line, not n-best lists")
+        dev = model_output.device
+        T = int(model_output.shape[0])
+        ctc, ent, _ = ops.ctc_entropy(model_output.detach(), lens, torch.from_numpy(lab[:, 0]).to(dev), torch.from_numpy(ln[:, 0]).to(dev),
+                                      self.canon(dev))
+        ctc, ent = one_copy([ctc.reshape(-1, 1, 1), ent.reshape(-1, 1, 1)])
+        frames = [min(max(int(v), 0), T) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+        return [(float(c), float(h), float(h) / n if n else 0.0) for c, h, n in zip(ctc.reshape(-1), ent.reshape(-1), frames)]
+
     def words(self, alignment):
         """The tokens of textutils.form_tokenized_words over the line's characters (u0020 separates words and is no token, every
         punctuation mark and digit is a token of its own), each a WordAlignment(token, first_frame, last_frame, min_conf, mean_logp):

@@ -1485,6 +1485,40 @@ def ctc_nbest(logits, lens, labels, label_lens, canon=None, weights=None):
     return (ctc[:, 0] if squeeze else ctc), dlogits
 
 
+def ctc_entropy(logits, lens, labels, label_lens, canon=None, coeff=None):
+    """CTC score, alignment entropy and their gradient (vocr_ctc_entropy) of ONE labelling per line.  `logits`, `lens`, `canon` as for
+    ctc_align; `labels` int32 device tensor [B,L], `label_lens` int32 [B]; `coeff` None or an fp32 device tensor [B,2] = (w_ctc, w_ent)
+    per line.  Returns, on the device, (ctc fp32 [B] = ln P_ctc(labels | x), the bits of ctc_nbest's; entropy fp32 [B] = the entropy in
+    nats of the posterior over the labelling's feasible alignments, 0 for a labelling without a score; dlogits), dlogits None without
+    coeff, else fp32 [T,B,V] = the gradient with respect to the raw logits of sum_b (w_ctc_b * ctc_b + w_ent_b * entropy_b) over the
+    lines with a score (rows past `lens` and the rows of a line without a score are zero).  Without coeff only the forward sweep runs."""
+    if labels.dim() != 2 or label_lens.dim() != 1:
+        raise RuntimeError("ctc_entropy: labels must be int32 [B,L] and label_lens int32 [B] (labels %s, label_lens %s)"
+                           % (tuple(labels.shape), tuple(label_lens.shape)))
+    logits, lens_dev, labels, label_lens, _, stride, M, _, _ = _labelling_args(
+        "ctc_entropy", "vocr_ctc_align_workspace_bytes", "2 <= V <= 256, T * B < 2^31", logits, lens, labels, label_lens, canon)
+    T, B, V = logits.shape
+    dev = logits.device
+    nbytes = _lib.load().vocr_ctc_entropy_workspace_bytes(T, B, V, M, 0 if coeff is None else 1)
+    if nbytes == 0:
+        raise RuntimeError("ctc_entropy: unsupported shape (T=%d B=%d V=%d label length %d; 2 <= V <= 256, label length <= 1663, "
+                           "B * 16 * T * (2 * label length + 1) bytes of lattices <= 2 GiB)" % (T, B, V, M))
+    dlogits = None
+    if coeff is not None:
+        _need_gpu(coeff)
+        if coeff.dtype != torch.float32 or tuple(coeff.shape) != (B, 2):
+            raise RuntimeError("ctc_entropy: coeff must be fp32 [B,2] = (w_ctc, w_ent) per line (coeff %s %s, B=%d)"
+                               % (tuple(coeff.shape), coeff.dtype, B))
+        coeff = coeff.detach().contiguous()
+        dlogits = torch.empty_like(logits)
+    ctc = torch.empty(B, dtype=torch.float32, device=dev)
+    ent = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    call("vocr_ctc_entropy", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(labels), _p(label_lens), stride, M, _p(coeff), _p(ctc),
+         _p(ent), _p(dlogits), _p(ws), ws.numel() * 4, _stream())
+    return ctc, ent, dlogits
+
+
 def ctc_keyword_scores(logits, lens, queries, query_lens, query_flags=None, canon=None):
     """CTC keyword search (vocr_ctc_keyword_scores) on raw logits [T,B,V]: for every (line, query) the natural log of the EXPECTED
     NUMBER of occurrences of the query as a contiguous substring of the collapsed labelling - exact, over all frame paths; min(1, count)
