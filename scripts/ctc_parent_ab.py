@@ -15,10 +15,13 @@ labelling (the sweep, the host preamble and the class rule the scorers of a know
   Bits: vocr_ctc_align, vocr_ctc_edit_scores and vocr_ctc_nbest_grad (with and without weights) on every case of tests/nbest_cases.py,
   the small exact cases of tests/test_align_cpu.py and tests/test_edit_cpu.py (what the GPU tests of both run), the empty and invalid
   labellings of their edge cases, and two lines of 4000 frames with 1796 and 1554 labels (beyond 1663 the alignment keeps its rows in
-  the workspace); vocr_ctc_keyword_scores on every call the tests of tests/test_kws_gpu.py make; vocr_ctc_beam_search and
+  the workspace); vocr_ctc_entropy, without and with its coefficients, on every case of tests/test_entropy_gpu.py (the seam shapes:
+  31 - 33 and 63 - 65 labels, lens 1 .. 17 and 65 .. 74, V 2 / 96 / 256, classes with -inf members, the bad and the empty line) and on
+  the 3500-frame line of 1554 labels alone (the two-row layout near its limit of 1663); vocr_ctc_keyword_scores on every call the tests of tests/test_kws_gpu.py make; vocr_ctc_beam_search and
   vocr_ctc_word_beam_search on one English-canon case each of tests/beam_cases.py.  SHA-256 of every output and of the whole workspace.
   Time: T 294, B 32, V 96 (scripts/align_bench.py, edit_bench.py, risk_bench.py), the n = 4 and n = 16 best of a K = 16 search on peaky
-  logits at p_char 0.35 (43 - 67 labels: the rows in LDS) and 0.10 (5 - 24 labels: one position per lane), packed to the longest.
+  logits at p_char 0.35 (43 - 67 labels: the rows in LDS) and 0.10 (5 - 24 labels: one position per lane), packed to the longest;
+  vocr_ctc_entropy on the 1-best of the same search, scores only and with the gradient.
 
 Bits, both: outputs and workspace are filled with a constant before the call, so bytes that no kernel writes compare equal trivially;
 every digest pair must be equal, and the script exits 1 otherwise.
@@ -48,12 +51,13 @@ FILL = -3.0
 TIMED = ("bench_full", "c4_ragged", "generic_long")
 
 
-# labelling: C entry -> (its workspace-size function, where that function's arguments sit in the entry's argument list, the output
-# pointers, the workspace pointer; the workspace's size follows it)
+# labelling: C entry -> (its workspace-size function, where that function's arguments sit in the entry's argument list - or a callable
+# of that list for one that is no argument of the entry -, the output pointers, the workspace pointer; the workspace's size follows it)
 ENTRIES = {
     "vocr_ctc_align": ("vocr_ctc_align_workspace_bytes", (2, 3, 4, 8, 10), (11, 12, 13), 14),
     "vocr_ctc_edit_scores": ("vocr_ctc_edit_workspace_bytes", (2, 3, 4, 8, 10), (11, 12, 13, 14), 15),
     "vocr_ctc_nbest_grad": ("vocr_ctc_nbest_workspace_bytes", (2, 3, 4, 8, 10), (12, 13), 14),
+    "vocr_ctc_entropy": ("vocr_ctc_entropy_workspace_bytes", (2, 3, 4, 9, lambda a: int(a[10] is not None)), (11, 12, 13), 14),
     "vocr_ctc_keyword_scores": ("vocr_ctc_keyword_workspace_bytes", (2, 3, 4, 9, 11), (12, 13, 14), 15),
     "vocr_ctc_beam_search": ("vocr_ctc_beam_workspace_bytes", (2, 3, 4, 6, 7), (16, 17, 18), 19),
     "vocr_ctc_word_beam_search": ("vocr_ctc_word_beam_workspace_bytes", (2, 3, 4, 6, 7), (29, 30, 31), 32),
@@ -144,7 +148,7 @@ class Replay:
 
     def sizes(self, lib):
         fn, where, _, _ = ENTRIES[self.name]
-        return getattr(lib, fn)(*[self.args[i] for i in where])
+        return getattr(lib, fn)(*[i(self.args) if callable(i) else self.args[i] for i in where])
 
     def digests(self, lib):
         for t in self.outs + [self.ws]:
@@ -199,6 +203,18 @@ def labelling_calls(x, lens, labels, label_lens, canon, w):
     return list(zip(("align", "edit", "nbest+w", "nbest"), calls))
 
 
+def entropy_calls(x, lens, labels, label_lens, canon, coeff):
+    """the two calls of the entropy entry on one batch of device tensors (labels [B,L]): scores only, and with the gradient"""
+    from vistaocr_amd import ops
+
+    def go():
+        ops.ctc_entropy(x, lens, labels, label_lens, canon)
+        ops.ctc_entropy(x, lens, labels, label_lens, canon, coeff)
+    calls = record(go)
+    assert [c.name for c in calls] == ["vocr_ctc_entropy"] * 2 and calls[0].args[10] is None and calls[1].args[10] is not None
+    return list(zip(("entropy", "entropy+c"), calls))
+
+
 def host_batch(x, lens, hyps, canon, width=None):
     """numpy logits [T,B,V] and hyps[b][q] (lists or None) as the device tensors of labelling_calls"""
     from tests import nbest_ref as nr
@@ -221,6 +237,7 @@ def labelling_bit_cases():
     from tests import test_align_cpu as tac
     from tests import test_beam_fp64_gpu as tb
     from tests import test_edit_cpu as tec
+    from tests import test_entropy_gpu as te
     from tests import test_kws_gpu as tk
     from tests import test_nbest_gpu as tn
     from tests import test_word_beam_fp64_gpu as tw
@@ -239,6 +256,11 @@ def labelling_bit_cases():
     hyps = [[ar.greedy_labels(x[:, b], ln)] for b, ln in enumerate((4000, 3500))]
     assert len(hyps[0][0]) > 1663 > len(hyps[1][0]) > 1000
     yield "T 4000, %d and %d labels" % (len(hyps[0][0]), len(hyps[1][0])), labelling_calls(*host_batch(x, [4000, 3500], hyps, None))
+    for c in te.CASES:
+        yield "entropy " + c[0], entropy_calls(*te._device_case(te.build_case(c[0])))
+    xd, lens, labels, label_lens, _, _ = host_batch(x[:3500, 1:2], [3500], [hyps[1]], None)
+    yield "T 3500, %d labels" % len(hyps[1][0]), entropy_calls(xd, lens, labels[:, 0].contiguous(), label_lens[:, 0].contiguous(), None,
+                                                             torch.tensor([[0.75, -0.5]], device="cuda"))
     kws = [(tk.test_query_lengths_and_lane_layouts, (L,)) for L in tk.QUERY_LENGTHS]
     kws += [(f, ()) for f in (tk.test_mixed_lengths_land_at_the_callers_index, tk.test_frame_counts,
                               tk.test_alphabet_sizes_classes_and_minus_infinity, tk.test_peak_before_the_start_and_after_the_end,
@@ -256,7 +278,8 @@ def labelling_bit_cases():
 
 
 def labelling_timed_cases():
-    """(shape name, longest labelling, [(entry label, Replay)]): the n best of a K = 16 search over the English classes"""
+    """(shape name, longest labelling, [(entry label, Replay)]): the n best of a K = 16 search over the English classes, and its 1-best
+    for the entropy entry"""
     import vistaocr_amd as va
     from tests import beam_data as bd
     from vistaocr_amd import ops
@@ -272,6 +295,10 @@ def labelling_timed_cases():
             M = max(int(ln.max()), 1)
             w = torch.linspace(-1.0, 1.0, B * n, device="cuda").reshape(B, n).contiguous()
             yield "p_char %.2f n %2d" % (p_char, n), M, labelling_calls(xd, lens, lab[:, :, :M].contiguous(), ln.contiguous(), cd, w)
+        lab, ln, _ = ops.ctc_beam_search(xd, [T] * B, cd, 16, 1)
+        M = max(int(ln.max()), 1)
+        coeff = torch.tensor([[1.0, -0.2]] * B, device="cuda")
+        yield "p_char %.2f 1-best" % p_char, M, entropy_calls(xd, lens, lab[:, 0, :M].contiguous(), ln[:, 0].contiguous(), cd, coeff)
 
 
 def labelling_tables(libs, args, say):
@@ -291,7 +318,7 @@ def labelling_tables(libs, args, say):
     say("")
     say("time: the whole call (class log-probabilities and every kernel behind them), HIP events, us; per round the median of a window of "
         "%d calls, the libraries alternating, %d rounds after a warm-up window of each" % (args.window, args.rounds))
-    tfmt = "%-16s %3s %-8s | %9s %9s %9s | %9s | %s"
+    tfmt = "%-17s %3s %-9s | %9s %9s %9s | %9s | %s"
     say(tfmt % ("shape", "M", "entry", "parent", "p. spread", "new", "new - p.", "new <= parent + spread"))
     slower = 0
     for shape, M, calls in labelling_timed_cases():

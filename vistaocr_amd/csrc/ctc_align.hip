@@ -22,8 +22,9 @@
 //   S  > 64 : both previous rows in LDS (in the workspace beyond 1663 labels, where they no longer fit), lanes over 64-position chunks, updated in place from the highest chunk down (a chunk reads
 //             only positions that no earlier chunk of the step wrote); the gathered log-probabilities of TB frames are staged into LDS
 //             in one pass of independent loads, so the L2 round trip is paid once per TB frames.
-// The recursion is the one of ctc_label_sweep (ctc_lattice.h), which the edit scores and the n-best gradient run, with the Viterbi row
-// beside it.  It is written out here and not an instantiation of that template: as one, the S > 64 loop compiled to the same
+// The recursion is the one of ctc_label_sweep (ctc_lattice.h) - the template over a cell type that the edit scores and the n-best
+// gradient run over SumCell and the alignment entropy over its (a, e) cell - with the Viterbi row and its back pointers beside the
+// sum.  It is written out here and not an instantiation of that template: as one, the S > 64 loop compiled to the same
 // instructions at another address and ran 1.4 % slower (profiles/ctc_labelling_ab.txt has the kept form's figures).  PF, TB, the
 // LDS size and the host side in front of the call are the header's.
 // Back pointers take 2 bits per (t, s): two wave ballots (bit 0, bit 1) per (t, 64-position chunk), 16 bytes, written by lane 0.

@@ -16,9 +16,10 @@
 // ("!=" compares classes).  Every sum cuts a path at its last frame in a given state, so no path is counted twice.
 //
 //   kernel 1  class log-probabilities : class_logprob_rows_kernel of the alignment, once per line.
-//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel: one wave per (line, hypothesis, direction) writes alpha or beta to the
-//                                       workspace, TRANSPOSED ([s][t]: kernel 3 walks one position through the frames), by
-//                                       ctc_label_sweep, which the n-best gradient runs too.  beta is alpha of the reversed labelling over the reversed
+//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel<SumCell, true>: one wave per (line, hypothesis, direction) writes alpha or
+//                                       beta to the workspace, TRANSPOSED ([s][t]: kernel 3 walks one position through the frames), by
+//                                       ctc_label_sweep over SumCell, the plain sum, which the n-best gradient runs too (the alignment
+//                                       entropy runs it over its own cell).  beta is alpha of the reversed labelling over the reversed
 //                                       frames, so both directions run the same code.  The forward wave also writes ln P_ctc(labels | x).
 //   kernel 3  edit scores             : one workgroup per (line, hypothesis, slot p), p = 0 .. max_label_len; thread c owns column c
 //                                       (coalesced class log-probabilities).  One pass over the frames serves the substitution at p,
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void ctc_edit_scores_kernel(const float* __res
 // kernel 3's grid, B * n * (max_label_len + 1) workgroups, is this entry's own limit
 LatticePlan edit_plan(int t, int b, int v, int n, int max_label_len) {
     if ((long)b * n * (max_label_len + 1) >= (1L << 31)) return LatticePlan{0, 0, 0, false};
-    return lattice_plan(t, b, v, n, max_label_len);
+    return lattice_plan(t, b, v, n, max_label_len, SumCell::ROWS);
 }
 
 }  // namespace
@@ -171,13 +172,13 @@ extern "C" int vocr_ctc_edit_scores(const float* logits, const int32_t* lens, in
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_edit_scores: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_lattice_kernel<true>};
+    const void* const big[] = {(const void*)ctc_lattice_kernel<SumCell, true>};
     if (vocr_allow_dynamic_lds(big, 1, (int)LDS_BUDGET, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     float* clp = (float*)workspace;
     float* lat = (float*)((char*)workspace + clp_bytes(t, b, v));
     if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
-    ctc_lattice_kernel<true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
-                                                     p.sp, lat, out_ctc);
+    ctc_lattice_kernel<SumCell, true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride,
+                                                                   max_label_len, p.sp, lat, out_ctc, nullptr);
     VOCR_CHECK_LAUNCH("vocr_ctc_edit_scores(lattices)");
     ctc_edit_scores_kernel<<<b * n * (max_label_len + 1), vocr_cdiv(v, 64) * 64, 0, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n,
                                                                                         label_stride, max_label_len, lat, out_sub,

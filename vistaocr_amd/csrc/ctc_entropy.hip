@@ -18,16 +18,17 @@
 // (m - a_i) + ln(sum), m the maximum, not as A - a_i.  A line with one feasible path has e = 0 in every cell and H = 0 exactly.
 //
 //   kernel 1  class log-probabilities : class_logprob_rows_kernel, once per line.
-//   kernel 2  paired sweep            : ctc_pair_sweep, the two row layouts of ctc_label_sweep (S <= 64 in registers with wave shuffles and
-//                                       the emissions prefetched, S > 64 in LDS in 64-position chunks with TB frames staged) with the e
-//                                       row beside the a row.  With coeff: one wave per (line, direction) writes its pair TRANSPOSED
-//                                       ([s][t]) to the workspace - the backward pair is the forward pair of the reversed labelling over
-//                                       the reversed frames: b includes frame t's emission, eb is the entropy over the partial paths that
+//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel with n = 1 over EntCell below, the (a, e) cell: ctc_label_sweep, the sweep
+//                                       of the edit scores and the n-best gradient in both of its row layouts, with the e row beside
+//                                       the a row.  With coeff: one wave per (line, direction) writes its pair TRANSPOSED ([s][t]) to
+//                                       the workspace - the backward pair is the forward pair of the reversed labelling over the
+//                                       reversed frames: b includes frame t's emission, eb is the entropy over the partial paths that
 //                                       START in (t, s) - and the forward wave out_ctc and out_entropy.  Without: the forward wave alone.
 //   kernel 3  gradient                : one wave per (line, tile of TT frames).  Lane (g, k) owns frame k of the tile for the positions
-//                                       s = g, g + SG, ..: it adds its term to ITS OWN accumulator of the position's class in LDS
-//                                       (acc[g][c][k]), so there is no atomic and every sum has a fixed order; then the row pass of
-//                                       ctc_nbest_grad_kernel (log-softmax again, the SG partial sums in order, one coalesced store).
+//                                       s = g, g + NG, ..: it adds its term to ITS OWN accumulator of the position's class in LDS
+//                                       (acc[g][c][k]), so there is no atomic and every sum has a fixed order; then ctc_grad_rows, the
+//                                       row pass the n-best gradient ends with (log-softmax again, the NG partial sums in order, one
+//                                       coalesced store).
 //
 // The gradient.  gam(t, s) = exp(a + b - u - ln P) is the posterior of position s at frame t and occ(t, c) its sum over the positions of
 // class c, as in vocr_ctc_nbest_grad.  With occN(t, c) = (1 / P) sum over the paths with pi_t = c of p * (-ln p):
@@ -41,20 +42,15 @@
 // pair at t with the successors' backward pair at t + 1) reads up to three successors' pairs per cell and needs the end states as a
 // special case, and buys nothing here.
 //
-// LIMIT: the S > 64 layout keeps two rows, ext and TB staged frames: pair_floats(sp) = 2 (sp + 2) + sp + TB sp = 11 sp + 4 floats <=
+// LIMIT: the S > 64 layout keeps two rows, ext and TB staged frames: sweep_floats(sp, 2) = 2 (sp + 2) + sp + TB sp = 11 sp + 4 floats <=
 // LDS_BUDGET / 4 = 36864 gives sp <= 3328 (52 chunks), so max_label_len <= 1663 (2 * 1663 + 1 = 3327), where the single-row scorers
 // reach 1823.
 #include "ctc_lattice.h"
 
 namespace {
 
-constexpr int TT = 16;                       // kernel 3: frames per workgroup
-constexpr int SG = 4;                        // kernel 3: position groups (TT * SG = 64 lanes)
-constexpr int ENTROPY_MAX_LABEL_LEN = 1663;
-
-// floats of the paired S > 64 layout: rows a and e of sp + 2, ext[sp], the staged log-probabilities [TB][sp]; 0 when one wave suffices
-__host__ __device__ constexpr size_t pair_floats(int sp) { return sp <= 64 ? 0 : 2 * (size_t)(sp + 2) + sp + (size_t)TB * sp; }
-static_assert(pair_floats(3328) * 4 <= LDS_BUDGET && pair_floats(3392) * 4 > LDS_BUDGET, "ENTROPY_MAX_LABEL_LEN");
+constexpr int ENTROPY_MAX_LABEL_LEN = 1663;    // what lattice_plan's LDS check admits for two rows; named for the error text
+static_assert(sweep_floats(3328, 2) * 4 <= LDS_BUDGET && sweep_floats(3392, 2) * 4 > LDS_BUDGET, "ENTROPY_MAX_LABEL_LEN");
 static_assert(2 * ENTROPY_MAX_LABEL_LEN + 1 <= 3328 && 2 * (ENTROPY_MAX_LABEL_LEN + 1) + 1 > 3328, "ENTROPY_MAX_LABEL_LEN");
 
 // The mixture of up to three disjoint path sets with log-masses a1..a3 and entropies e1..e3: A = lse3(a1, a2, a3) in lse3's own
@@ -77,147 +73,32 @@ __device__ __forceinline__ Mix mix3(float a1, float a2, float a3, float e1, floa
     return {lg + m, acc / sum};
 }
 
-// ctc_label_sweep with the e row beside the a row; map.dst takes the a cells and map.dst + eoff the e cells.  rows: pair_floats(SP).
-// Returns ln P and H from the two end states.
-template <bool STORED>
-__device__ __forceinline__ Mix ctc_pair_sweep(const float* __restrict__ lpb, long tstride, const int32_t* __restrict__ canon,
-                                              const int32_t* __restrict__ lab, int len, int S, int SP, float* rows,
-                                              const SweepMap<STORED>& map, long eoff, int lane) {
-    if (S <= 64) {
-        const bool in = lane < S;
-        const int e = (in && (lane & 1)) ? map.label(lab, lane >> 1) : 0;
-        const int c = class_of(canon, e);
-        const int c_m2 = __shfl_up(c, 2, 64);
-        const bool skip = lane >= 2 && e != 0 && c != c_m2;
-        const float* col = lpb + e;
-        float* out = STORED ? map.dst + (long)map.pos(in ? lane : 0) * map.T : nullptr;
-        float vs = NEG_INF, es = 0.f;
-        if (lane == 0 || (lane == 1 && S > 1)) vs = col[(long)map.frame(0) * tstride];
-        if (STORED && in) {
-            out[map.frame(0)] = vs;
-            out[eoff + map.frame(0)] = 0.f;
-        }
-        float buf[PF];
-#pragma unroll
-        for (int k = 0; k < PF; ++k) buf[k] = col[(long)map.frame(min(1 + k, len - 1)) * tstride];
-        for (int t0 = 1; t0 < len; t0 += PF) {
-#pragma unroll
-            for (int k = 0; k < PF; ++k) {
-                const int t = t0 + k;
-                if (t < len) {                                   // wave-uniform
-                    const float lpe = buf[k];
-                    buf[k] = col[(long)map.frame(min(t + PF, len - 1)) * tstride];
-                    float a2 = __shfl_up(vs, 1, 64), a3 = __shfl_up(vs, 2, 64);
-                    const float e2 = __shfl_up(es, 1, 64), e3 = __shfl_up(es, 2, 64);
-                    if (lane < 1) a2 = NEG_INF;
-                    if (!skip) a3 = NEG_INF;
-                    const Mix mx = mix3(vs, a2, a3, es, e2, e3);
-                    vs = in ? mx.A + lpe : NEG_INF;
-                    es = (in && vs > NEG_INF) ? mx.e : 0.f;
-                    if (STORED && in) {
-                        out[map.frame(t)] = vs;
-                        out[eoff + map.frame(t)] = es;
-                    }
-                }
-            }
-        }
-        const bool two = S > 1;
-        return mix3(__shfl(vs, S - 1, 64), two ? __shfl(vs, S - 2, 64) : NEG_INF, NEG_INF, __shfl(es, S - 1, 64),
-                    two ? __shfl(es, S - 2, 64) : 0.f, 0.f);
+// The cell of ctc_label_sweep that carries the pair.  kill() masks a alone: mix3 gives a set at -inf no share, whatever its e.  A cell
+// without a path has e = 0.  finish(): ln P and H, the mixture of the two end cells.
+struct EntCell {
+    static constexpr int ROWS = 2;
+    static constexpr bool ENTROPY = true;
+    float a, e;
+    static __device__ __forceinline__ EntCell none() { return {NEG_INF, 0.f}; }
+    static __device__ __forceinline__ EntCell first(float u) { return {u, 0.f}; }
+    static __device__ __forceinline__ EntCell step(EntCell p1, EntCell p2, EntCell p3, float u) {
+        const Mix mx = mix3(p1.a, p2.a, p3.a, p1.e, p2.e, p3.e);
+        const float a = mx.A + u;
+        return {a, a > NEG_INF ? mx.e : 0.f};
     }
-    float* ra = rows;                                            // ra[2 + s]
-    float* re = rows + SP + 2;                                   // re[2 + s]
-    int* ext = (int*)(rows + 2 * (SP + 2));                      // label | class << 16
-    float* em = rows + 2 * (SP + 2) + SP;                        // em[k * SP + s]
-    const int NC = (S + 63) >> 6;
-    for (int s = lane; s < S; s += 64) {
-        const int e = (s & 1) ? map.label(lab, s >> 1) : 0;
-        ext[s] = e | (class_of(canon, e) << 16);
-        const float v = s < 2 ? lpb[(long)map.frame(0) * tstride + e] : NEG_INF;
-        ra[2 + s] = v;
-        re[2 + s] = 0.f;
-        if (STORED) {
-            float* o = map.dst + (long)map.pos(s) * map.T + map.frame(0);
-            o[0] = v;
-            o[eoff] = 0.f;
-        }
+    __device__ __forceinline__ void kill() { a = NEG_INF; }
+    __device__ __forceinline__ EntCell up(int d) const { return {__shfl_up(a, d, 64), __shfl_up(e, d, 64)}; }
+    __device__ __forceinline__ EntCell from(int l) const { return {__shfl(a, l, 64), __shfl(e, l, 64)}; }
+    static __device__ __forceinline__ EntCell get(const float* p, long stride, long i) { return {p[i], p[stride + i]}; }
+    __device__ __forceinline__ void put(float* p, long stride, long i) const { p[i] = a, p[stride + i] = e; }
+    static __device__ __forceinline__ void finish(EntCell as, EntCell cs, float* out_ctc, float* out_entropy, int i) {
+        const Mix end = mix3(as.a, cs.a, NEG_INF, as.e, cs.e, 0.f);
+        out_ctc[i] = end.A;
+        out_entropy[i] = fmaxf(end.e, 0.f);                      // 0 without a path
     }
-    if (lane < 2) ra[lane] = NEG_INF, re[lane] = 0.f;
-    __syncthreads();
-    for (int t0 = 1; t0 < len; t0 += TB) {
-        const int nk = min(TB, len - t0);
-        for (int s = lane; s < S; s += 64) {
-            const float* col = lpb + (ext[s] & 0xffff);
-#pragma unroll
-            for (int k = 0; k < TB; ++k)
-                if (k < nk) em[k * SP + s] = col[(long)map.frame(t0 + k) * tstride];
-        }
-        __syncthreads();
-        for (int k = 0; k < nk; ++k) {
-            const int ft = map.frame(t0 + k);
-            for (int ch = NC - 1; ch >= 0; --ch) {
-                const int s = ch * 64 + lane;
-                const bool in = s < S;
-                float na = NEG_INF, ne = 0.f;
-                if (in) {
-                    const int x = ext[s];
-                    const bool skip = s >= 2 && (x & 0xffff) != 0 && (x >> 16) != (ext[s - 2] >> 16);
-                    const Mix mx = mix3(ra[2 + s], ra[1 + s], skip ? ra[s] : NEG_INF, re[2 + s], re[1 + s], re[s]);
-                    na = mx.A + em[k * SP + s];
-                    ne = na > NEG_INF ? mx.e : 0.f;
-                }
-                __builtin_amdgcn_wave_barrier();                 // every lane of the chunk has read before any writes
-                if (in) {
-                    ra[2 + s] = na;
-                    re[2 + s] = ne;
-                    if (STORED) {
-                        float* o = map.dst + (long)map.pos(s) * map.T + ft;
-                        o[0] = na;
-                        o[eoff] = ne;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    return mix3(ra[2 + S - 1], ra[2 + S - 2], NEG_INF, re[2 + S - 1], re[2 + S - 2], 0.f);
-}
+};
 
-// LATTICE: grid.x = B * 2 (direction fastest), 64 threads: the forward and the backward pair of every line to
-// lat: [B][2 directions][2 rows (a, e)][SM = 2 * max_label_len + 1][T] floats; the forward wave writes out_ctc and out_entropy.
-// !LATTICE: scores only - grid.x = B, the forward wave alone, nothing written to lat.
-// Dynamic LDS (S > 64 only): pair_floats(SP) floats.
-template <bool LATTICE>
-__global__ __launch_bounds__(64) void ctc_entropy_sweep_kernel(const float* __restrict__ clp, const int32_t* __restrict__ lens,
-                                                               const int32_t* __restrict__ canon, const int32_t* __restrict__ labels,
-                                                               const int32_t* __restrict__ label_lens, int T, int B, int V,
-                                                               int label_stride, int max_label_len, int SP, float* __restrict__ lat,
-                                                               float* __restrict__ out_ctc, float* __restrict__ out_entropy) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int lane = threadIdx.x;
-    const int b = LATTICE ? blockIdx.x >> 1 : blockIdx.x, dir = LATTICE ? blockIdx.x & 1 : 0;
-    const int len = min(max(lens[b], 0), T);
-    const int L = label_lens[b];
-    const int32_t* lab = labels + (long)b * label_stride;
-    const bool bad = labelling_bad(canon, lab, L, V, max_label_len, lane);
-    if (bad || len == 0) {                                      // nobody reads a lattice of such a line
-        if (dir == 0 && lane == 0) {
-            out_ctc[b] = (!bad && L == 0) ? 0.f : NEG_INF;
-            out_entropy[b] = 0.f;
-        }
-        return;
-    }
-    const int S = 2 * L + 1;
-    const long SM = 2 * (long)max_label_len + 1;
-    const SweepMap<LATTICE> map = {dir, len, S, L, T, LATTICE ? lat + ((long)b * 2 + dir) * 2 * SM * T : nullptr};
-    const Mix end = ctc_pair_sweep(clp + (long)b * V, (long)B * V, canon, lab, len, S, SP, sm, map, SM * T, lane);
-    if (dir == 0 && lane == 0) {
-        out_ctc[b] = end.A;
-        out_entropy[b] = fmaxf(end.e, 0.f);                      // 0 without a path
-    }
-}
-
-// grid.x = B * ceil(T / TT) (tile fastest), 64 threads.  Dynamic LDS: acc[SG][V][TT] floats.
+// grid.x = B * ceil(T / TT) (tile fastest), 64 threads.  Dynamic LDS: acc[NG][V][TT] floats.
 __global__ __launch_bounds__(64) void ctc_entropy_grad_kernel(const float* __restrict__ logits, const float* __restrict__ clp,
                                                               const int32_t* __restrict__ lens, const int32_t* __restrict__ canon,
                                                               const int32_t* __restrict__ labels, const int32_t* __restrict__ label_lens,
@@ -234,7 +115,7 @@ __global__ __launch_bounds__(64) void ctc_entropy_grad_kernel(const float* __res
     const float sc = scores[b];
     const bool scored = sc > NEG_INF;                            // no path: the line's rows are zeros
     const float wc = coeff[2 * b], we = coeff[2 * b + 1];
-    for (int i = lane; i < SG * V * TT; i += 64) acc[i] = 0.f;
+    for (int i = lane; i < NG * V * TT; i += 64) acc[i] = 0.f;
     __syncthreads();
     if (scored && t < len) {
         const float* lpt = clp + (long)t * tstride + (long)b * V;               // the frame's class log-probabilities
@@ -245,7 +126,7 @@ __global__ __launch_bounds__(64) void ctc_entropy_grad_kernel(const float* __res
         const float* fa = lat + (long)b * 4 * SM * T + t;                       // a, ef, b, eb: planes of SM * T
         float* mine = acc + (long)g * V * TT + k;                               // mine[c * TT]
 #pragma unroll 2
-        for (int s = g; s < S; s += SG) {
+        for (int s = g; s < S; s += NG) {
             const float a = fa[(long)s * T], be = fa[(2 * SM + s) * T];
             if (a == NEG_INF || be == NEG_INF) continue;
             const int e = (s & 1) ? lab[s >> 1] : 0;
@@ -256,51 +137,13 @@ __global__ __launch_bounds__(64) void ctc_entropy_grad_kernel(const float* __res
         }
     }
     __syncthreads();
-    for (int kk = 0; kk < TT; ++kk) {
-        const int tr = t0 + kk;
-        if (tr >= T) break;
-        const long row = (long)tr * B + b;
-        float* out = dlogits + row * V;
-        if (tr >= len || !scored) {
-            for (int v = lane; v < V; v += 64) out[v] = 0.f;
-            continue;
-        }
-        const float* xr = logits + row * V;
-        const float* cr = clp + row * V;
-        const RowLse rl = wave_row_lse(xr, V, lane);
-        for (int v = lane; v < V; v += 64) {
-            const float lpv = row_logprob(rl, xr, v);
-            const float* a = acc + (long)class_of(canon, v) * TT + kk;
-            float G = a[0];
-#pragma unroll
-            for (int j = 1; j < SG; ++j) G += a[(long)j * V * TT];
-            const float share = (lpv == NEG_INF) ? 0.f : expf(lpv - cr[v]);     // p_t(v) / P_t(class(v))
-            out[v] = share * G - expf(lpv) * wc;
-        }
-    }
-}
-
-struct EntropyPlan {
-    int sp;
-    size_t lds, lattice_bytes;
-    bool ok;
-};
-
-inline EntropyPlan entropy_plan(int t, int b, int v, int max_label_len) {
-    EntropyPlan p = {0, 0, 0, false};
-    const LabelPlan lp = label_plan(t, b, v, 1, max_label_len);
-    if (!lp.ok) return p;
-    p.sp = lp.sp;
-    p.lds = pair_floats(p.sp) * 4;
-    p.lattice_bytes = (size_t)b * 4 * (2 * (size_t)max_label_len + 1) * t * sizeof(float);
-    p.ok = max_label_len <= ENTROPY_MAX_LABEL_LEN && p.lds <= LDS_BUDGET && p.lattice_bytes <= LATTICE_BYTES_MAX;
-    return p;
+    ctc_grad_rows(logits, clp, canon, acc, T, B, V, b, t0, scored ? len : 0, wc, dlogits, lane);
 }
 
 }  // namespace
 
 extern "C" size_t vocr_ctc_entropy_workspace_bytes(int t, int b, int v, int max_label_len, int want_grad) {
-    const EntropyPlan p = entropy_plan(t, b, v, max_label_len);
+    const LatticePlan p = lattice_plan(t, b, v, 1, max_label_len, EntCell::ROWS);
     if (!p.ok) return 0;
     return clp_bytes(t, b, v) + (want_grad ? p.lattice_bytes : 0);
 }
@@ -314,7 +157,7 @@ extern "C" int vocr_ctc_entropy(const float* logits, const int32_t* lens, int t,
     VOCR_CHECK_ARG(!coeff == !dlogits, "vocr_ctc_entropy: coeff and dlogits go together (coeff %s, dlogits %s)", coeff ? "given" : "NULL",
                    dlogits ? "given" : "NULL");
     if (check_labelling_shape(who, t, b, v, 1, label_stride, max_label_len) != VOCR_OK) return VOCR_EINVAL;
-    const EntropyPlan p = entropy_plan(t, b, v, max_label_len);
+    const LatticePlan p = lattice_plan(t, b, v, 1, max_label_len, EntCell::ROWS);
     VOCR_CHECK_ARG(p.ok, "vocr_ctc_entropy: unsupported shape (t=%d b=%d v=%d max_label_len=%d): need max_label_len <= %d (the paired rows "
                    "of the sweep in the LDS) and the four lattices (%zu bytes) within %zu bytes", t, b, v, max_label_len,
                    ENTROPY_MAX_LABEL_LEN, p.lattice_bytes, LATTICE_BYTES_MAX);
@@ -323,22 +166,22 @@ extern "C" int vocr_ctc_entropy(const float* logits, const int32_t* lens, int t,
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_entropy: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_entropy_sweep_kernel<true>, (const void*)ctc_entropy_sweep_kernel<false>,
+    const void* const big[] = {(const void*)ctc_lattice_kernel<EntCell, true>, (const void*)ctc_lattice_kernel<EntCell, false>,
                                (const void*)ctc_entropy_grad_kernel};
     if (vocr_allow_dynamic_lds(big, 3, (int)LDS_BUDGET, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     float* clp = (float*)workspace;
     float* lat = (float*)((char*)workspace + clp_bytes(t, b, v));
     if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
     if (!coeff) {
-        ctc_entropy_sweep_kernel<false><<<b, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, label_stride, max_label_len,
-                                                            p.sp, nullptr, out_ctc, out_entropy);
+        ctc_lattice_kernel<EntCell, false><<<b, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, 1, label_stride,
+                                                               max_label_len, p.sp, nullptr, out_ctc, out_entropy);
         VOCR_CHECK_LAUNCH("vocr_ctc_entropy(scores)");
         return VOCR_OK;
     }
-    ctc_entropy_sweep_kernel<true><<<b * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, label_stride, max_label_len,
-                                                           p.sp, lat, out_ctc, out_entropy);
+    ctc_lattice_kernel<EntCell, true><<<b * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, 1, label_stride,
+                                                              max_label_len, p.sp, lat, out_ctc, out_entropy);
     VOCR_CHECK_LAUNCH("vocr_ctc_entropy(lattices)");
-    ctc_entropy_grad_kernel<<<b * vocr_cdiv(t, TT), 64, (size_t)SG * v * TT * sizeof(float), s>>>(
+    ctc_entropy_grad_kernel<<<b * vocr_cdiv(t, TT), 64, (size_t)NG * v * TT * sizeof(float), s>>>(
         logits, clp, lens, canon, labels, label_lens, t, b, v, label_stride, max_label_len, lat, out_ctc, out_entropy, coeff, dlogits);
     VOCR_CHECK_LAUNCH("vocr_ctc_entropy(gradient)");
     return VOCR_OK;

@@ -12,29 +12,26 @@
 // the sums over the hypotheses with a finite score.
 //
 //   kernel 1  class log-probabilities : class_logprob_rows_kernel of the alignment, once per line.
-//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel, as the edit scores.  With weights: one wave per (line, hypothesis,
-//                                       direction) writes alpha or beta TRANSPOSED ([s][t]) to the workspace and the forward wave
-//                                       out_ctc.  Without: the forward wave alone, nothing stored.  out_ctc holds the bits of
-//                                       vocr_ctc_edit_scores's either way.
+//   kernel 2  lattices (ctc_lattice.h): ctc_lattice_kernel over SumCell (ctc_label_sweep's plain sum), as the edit scores.  With
+//                                       weights: one wave per (line, hypothesis, direction) writes alpha or beta TRANSPOSED ([s][t])
+//                                       to the workspace and the forward wave out_ctc.  Without: the forward wave alone, nothing
+//                                       stored.  out_ctc holds the bits of vocr_ctc_edit_scores's either way.
 //   kernel 3  gradient                : one wave per (line, tile of TT frames).  Lane (g, k) owns frame k of the tile for the
-//                                       hypotheses q = g, g + QG, ..: it walks their positions s in order and adds
+//                                       hypotheses q = g, g + NG, ..: it walks their positions s in order and adds
 //                                       w_q * exp(alpha + beta - ln P_t(c) - ln P_q) to ITS OWN accumulator of class c in LDS
 //                                       (acc[g][c][k]: consecutive lanes, consecutive banks), reading alpha and beta along t
 //                                       (coalesced, TT * 4 bytes per position).  No two lanes share an accumulator, so there is no
-//                                       reduction inside the loop, no atomic, and the order of every sum is fixed.  Then, frame by
-//                                       frame, the lanes stride over the row's columns: the row's log-softmax again (wave_row_lse, the
-//                                       function kernel 1 calls: with no classes the member share is exactly 1), the QG partial sums added in
-//                                       order, one coalesced store of the row.  Rows t >= lens[b] are written as zeros.
+//                                       reduction inside the loop, no atomic, and the order of every sum is fixed.  Then
+//                                       ctc_grad_rows (ctc_lattice.h), the row pass shared with the entropy's gradient: frame by
+//                                       frame the row's log-softmax again, the NG partial sums added in order, one coalesced store of
+//                                       the row.  Rows t >= lens[b] are written as zeros.
 // A term with alpha or beta at -inf is skipped and a column with p_t(v) = 0 gets share 0, so a class with P_t(c) = 0 never meets a
 // division; a hypothesis with a -inf score is skipped whole, whatever its weight.  A line's rows are computed from that line alone.
 #include "ctc_lattice.h"
 
 namespace {
 
-constexpr int TT = 16;                       // kernel 3: frames per workgroup
-constexpr int QG = 4;                        // kernel 3: hypothesis groups (TT * QG = 64 lanes)
-
-// grid.x = B * ceil(T / TT) (tile fastest), 64 threads.  Dynamic LDS: acc[QG][V][TT] floats.
+// grid.x = B * ceil(T / TT) (tile fastest), 64 threads.  Dynamic LDS: acc[NG][V][TT] floats.
 __global__ __launch_bounds__(64) void ctc_nbest_grad_kernel(const float* __restrict__ logits, const float* __restrict__ clp,
                                                             const int32_t* __restrict__ lens, const int32_t* __restrict__ canon,
                                                             const int32_t* __restrict__ labels, const int32_t* __restrict__ label_lens,
@@ -47,14 +44,14 @@ __global__ __launch_bounds__(64) void ctc_nbest_grad_kernel(const float* __restr
     const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * TT, t = t0 + k;
     const int len = min(max(lens[b], 0), T);
     const long tstride = (long)B * V;
-    for (int i = lane; i < QG * V * TT; i += 64) acc[i] = 0.f;
+    for (int i = lane; i < NG * V * TT; i += 64) acc[i] = 0.f;
     __syncthreads();
     const bool live = t < len;
     const float* lpt = clp + (long)(live ? t : 0) * tstride + (long)b * V;      // the frame's class log-probabilities
     const long SM = 2 * (long)max_label_len + 1;
     float* mine = acc + (long)g * V * TT + k;                                   // mine[c * TT]
     float wsum = 0.f;                                                            // of this lane's hypotheses; the same for every k
-    for (int q = g; q < n; q += QG) {
+    for (int q = g; q < n; q += NG) {
         const int prob = b * n + q;
         const float sc = scores[prob];
         if (!(sc > NEG_INF)) continue;                                           // no path: contributes nothing
@@ -76,36 +73,15 @@ __global__ __launch_bounds__(64) void ctc_nbest_grad_kernel(const float* __restr
     }
     float wtot = __shfl(wsum, 0, 64);
 #pragma unroll
-    for (int j = 1; j < QG; ++j) wtot += __shfl(wsum, j * TT, 64);
+    for (int j = 1; j < NG; ++j) wtot += __shfl(wsum, j * TT, 64);
     __syncthreads();
-    for (int kk = 0; kk < TT; ++kk) {
-        const int tr = t0 + kk;
-        if (tr >= T) break;
-        const long row = (long)tr * B + b;
-        float* out = dlogits + row * V;
-        if (tr >= len) {
-            for (int v = lane; v < V; v += 64) out[v] = 0.f;
-            continue;
-        }
-        const float* xr = logits + row * V;
-        const float* cr = clp + row * V;
-        const RowLse rl = wave_row_lse(xr, V, lane);
-        for (int v = lane; v < V; v += 64) {
-            const float lpv = row_logprob(rl, xr, v);
-            const float* a = acc + (long)class_of(canon, v) * TT + kk;
-            float G = a[0];
-#pragma unroll
-            for (int j = 1; j < QG; ++j) G += a[(long)j * V * TT];
-            const float share = (lpv == NEG_INF) ? 0.f : expf(lpv - cr[v]);     // p_t(v) / P_t(class(v))
-            out[v] = share * G - expf(lpv) * wtot;
-        }
-    }
+    ctc_grad_rows(logits, clp, canon, acc, T, B, V, b, t0, len, wtot, dlogits, lane);
 }
 
 }  // namespace
 
 extern "C" size_t vocr_ctc_nbest_workspace_bytes(int t, int b, int v, int n, int max_label_len) {
-    const LatticePlan p = lattice_plan(t, b, v, n, max_label_len);
+    const LatticePlan p = lattice_plan(t, b, v, n, max_label_len, SumCell::ROWS);
     if (!p.ok) return 0;
     return clp_bytes(t, b, v) + p.lattice_bytes;
 }
@@ -119,7 +95,7 @@ extern "C" int vocr_ctc_nbest_grad(const float* logits, const int32_t* lens, int
     VOCR_CHECK_ARG(!weights == !dlogits, "vocr_ctc_nbest_grad: weights and dlogits go together (weights %s, dlogits %s)",
                    weights ? "given" : "NULL", dlogits ? "given" : "NULL");
     if (check_labelling_shape(who, t, b, v, n, label_stride, max_label_len) != VOCR_OK) return VOCR_EINVAL;
-    const LatticePlan p = lattice_plan(t, b, v, n, max_label_len);
+    const LatticePlan p = lattice_plan(t, b, v, n, max_label_len, SumCell::ROWS);
     VOCR_CHECK_ARG(p.ok, "vocr_ctc_nbest_grad: unsupported shape (t=%d b=%d v=%d n=%d max_label_len=%d): the lattices of all "
                    "labellings (%zu bytes) must fit %zu bytes and one row of the sweep (%zu bytes) the LDS", t, b, v, n, max_label_len,
                    p.lattice_bytes, LATTICE_BYTES_MAX, p.lds);
@@ -128,21 +104,22 @@ extern "C" int vocr_ctc_nbest_grad(const float* logits, const int32_t* lens, int
     VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_nbest_grad: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_lattice_kernel<true>, (const void*)ctc_lattice_kernel<false>, (const void*)ctc_nbest_grad_kernel};
+    const void* const big[] = {(const void*)ctc_lattice_kernel<SumCell, true>, (const void*)ctc_lattice_kernel<SumCell, false>,
+                               (const void*)ctc_nbest_grad_kernel};
     if (vocr_allow_dynamic_lds(big, 3, (int)LDS_BUDGET, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     float* clp = (float*)workspace;
     float* lat = (float*)((char*)workspace + clp_bytes(t, b, v));
     if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
     if (!weights) {
-        ctc_lattice_kernel<false><<<b * n, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
-                                                           p.sp, nullptr, out_ctc);
+        ctc_lattice_kernel<SumCell, false><<<b * n, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride,
+                                                                    max_label_len, p.sp, nullptr, out_ctc, nullptr);
         VOCR_CHECK_LAUNCH("vocr_ctc_nbest_grad(scores)");
         return VOCR_OK;
     }
-    ctc_lattice_kernel<true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len,
-                                                          p.sp, lat, out_ctc);
+    ctc_lattice_kernel<SumCell, true><<<b * n * 2, 64, p.lds, s>>>(clp, lens, canon, labels, label_lens, t, b, v, n, label_stride,
+                                                                   max_label_len, p.sp, lat, out_ctc, nullptr);
     VOCR_CHECK_LAUNCH("vocr_ctc_nbest_grad(lattices)");
-    ctc_nbest_grad_kernel<<<b * vocr_cdiv(t, TT), 64, (size_t)QG * v * TT * sizeof(float), s>>>(
+    ctc_nbest_grad_kernel<<<b * vocr_cdiv(t, TT), 64, (size_t)NG * v * TT * sizeof(float), s>>>(
         logits, clp, lens, canon, labels, label_lens, t, b, v, n, label_stride, max_label_len, lat, out_ctc, weights, dlogits);
     VOCR_CHECK_LAUNCH("vocr_ctc_nbest_grad(gradient)");
     return VOCR_OK;

@@ -1279,6 +1279,24 @@ def clamp_(x, clamp):
     return x
 
 
+def _lens_canon(what, logits, lens, canon):
+    """What every CTC entry over raw logits [T,B,V] does with `lens` (any int sequence or tensor: the frames of each line) and `canon`
+    (int32 [V] device tensor of the symbol classes or None): returns lens as an int32 device tensor of B entries, and checks canon."""
+    _, B, V = logits.shape
+    dev = logits.device
+    if torch.is_tensor(lens):
+        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    if lens_dev.numel() != B:
+        raise RuntimeError("%s: %d lengths for %d lines" % (what, lens_dev.numel(), B))
+    if canon is not None:
+        _need_gpu(canon)
+        if canon.dtype != torch.int32 or canon.numel() != V:
+            raise RuntimeError("%s: canon must be int32 [V]" % what)
+    return lens_dev
+
+
 def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None):
     """CTC prefix beam search (vocr_ctc_beam_search) over raw logits [T,B,V].  `lens`: the frames of each line (any int sequence or
     tensor), `canon`: int32 [V] device tensor of the symbol classes or None, `lm`: a dict of the device tables lm_logp [S,V] fp32,
@@ -1293,16 +1311,7 @@ def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weig
     if nbytes == 0:
         raise RuntimeError("ctc_beam_search: unsupported shape or beam (T=%d B=%d V=%d beam=%d nbest=%d; V <= 256, 1 <= nbest <= beam "
                            "<= 128)" % (T, B, V, beam, nbest))
-    if torch.is_tensor(lens):
-        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
-    if lens_dev.numel() != B:
-        raise RuntimeError("ctc_beam_search: %d lengths for %d lines" % (lens_dev.numel(), B))
-    if canon is not None:
-        _need_gpu(canon)
-        if canon.dtype != torch.int32 or canon.numel() != V:
-            raise RuntimeError("ctc_beam_search: canon must be int32 [V]")
+    lens_dev = _lens_canon("ctc_beam_search", logits, lens, canon)
     labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
     out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
     scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
@@ -1341,16 +1350,7 @@ def ctc_word_beam_search(logits, lens, canon, lm, beam=16, nbest=1, lm_weight=0.
     if nbytes == 0:
         raise RuntimeError("ctc_word_beam_search: unsupported shape or beam (T=%d B=%d V=%d beam=%d nbest=%d; V <= 256, 1 <= nbest <= "
                            "beam <= 128)" % (T, B, V, beam, nbest))
-    if torch.is_tensor(lens):
-        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
-    if lens_dev.numel() != B:
-        raise RuntimeError("ctc_word_beam_search: %d lengths for %d lines" % (lens_dev.numel(), B))
-    if canon is not None:
-        _need_gpu(canon)
-        if canon.dtype != torch.int32 or canon.numel() != V:
-            raise RuntimeError("ctc_word_beam_search: canon must be int32 [V]")
+    lens_dev = _lens_canon("ctc_word_beam_search", logits, lens, canon)
     tabs = [lm[k] for k in _WORD_LM_INT + _WORD_LM_FLOAT]
     _need_gpu(*tabs)
     bad = [k for k in _WORD_LM_INT if lm[k].dtype != torch.int32 or not lm[k].is_contiguous()]
@@ -1375,9 +1375,10 @@ def ctc_word_beam_search(logits, lens, canon, lm, beam=16, nbest=1, lm_weight=0.
     return labels, out_lens, scores
 
 
-def _labelling_args(what, workspace_fn, limits, logits, lens, labels, label_lens, canon):
-    """The argument checks and the 2-d / 3-d label convention ctc_align and ctc_edit_scores share.  Returns (logits, lens_dev, labels,
-    label_lens, n, stride, M, workspace bytes, squeeze)."""
+def _labelling_args(what, workspace_bytes, limits, logits, lens, labels, label_lens, canon):
+    """The argument checks and the 2-d / 3-d label convention the entries over known labellings share.  `workspace_bytes`: the entry's
+    workspace size as a callable of (T, B, V, n, M), 0 for a shape outside `limits` (or it raises its own error for one).  Returns (logits, lens_dev, labels, label_lens, n,
+    stride, M, workspace bytes, squeeze)."""
     _need_gpu(logits, labels, label_lens)
     logits = _f32c(logits)
     T, B, V = logits.shape
@@ -1394,19 +1395,10 @@ def _labelling_args(what, workspace_fn, limits, logits, lens, labels, label_lens
     if stride == 0:                                         # nothing to point at: one unused label per hypothesis
         labels, stride = torch.zeros(B, n, 1, dtype=torch.int32, device=dev), 1
     M = min(stride, T)
-    nbytes = getattr(_lib.load(), workspace_fn)(T, B, V, n, M)
+    nbytes = workspace_bytes(T, B, V, n, M)
     if nbytes == 0:
         raise RuntimeError("%s: unsupported shape (T=%d B=%d V=%d n=%d label length %d; %s)" % (what, T, B, V, n, M, limits))
-    if torch.is_tensor(lens):
-        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
-    if lens_dev.numel() != B:
-        raise RuntimeError("%s: %d lengths for %d lines" % (what, lens_dev.numel(), B))
-    if canon is not None:
-        _need_gpu(canon)
-        if canon.dtype != torch.int32 or canon.numel() != V:
-            raise RuntimeError("%s: canon must be int32 [V]" % what)
+    lens_dev = _lens_canon(what, logits, lens, canon)
     return logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze
 
 
@@ -1417,7 +1409,7 @@ def ctc_align(logits, lens, labels, label_lens, canon=None):
     (scores fp32 [B,n,2] = ln P(best path), ln P_ctc(labels | x); spans int32 [B,n,M,2] = first, last frame of each label, -1 where
     there is none; label_scores fp32 [B,n,M,2] = peak, sum of the frame log-probability over the span), M = min(L, T) but at least 1."""
     logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze = _labelling_args(
-        "ctc_align", "vocr_ctc_align_workspace_bytes", "2 <= V <= 256, n <= 128, T * B * n < 2^31", logits, lens, labels, label_lens, canon)
+        "ctc_align", _lib.load().vocr_ctc_align_workspace_bytes, "2 <= V <= 256, n <= 128, T * B * n < 2^31", logits, lens, labels, label_lens, canon)
     T, B, V = logits.shape
     dev = logits.device
     scores = torch.empty(B, n, 2, dtype=torch.float32, device=dev)
@@ -1439,7 +1431,7 @@ def ctc_edit_scores(logits, lens, labels, label_lens, canon=None):
     label p removed; ins [B,n,M+1,V] = at [q][c] the score with the class of column c inserted before label q, q = label length
     appends).  Entries beyond a labelling's length are -inf."""
     logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze = _labelling_args(
-        "ctc_edit_scores", "vocr_ctc_edit_workspace_bytes",
+        "ctc_edit_scores", _lib.load().vocr_ctc_edit_workspace_bytes,
         "2 <= V <= 256, n <= 128, label length <= 1823, B * n * 8 * T * (2 * label length + 1) bytes of lattices <= 2 GiB",
         logits, lens, labels, label_lens, canon)
     T, B, V = logits.shape
@@ -1463,7 +1455,7 @@ def ctc_nbest(logits, lens, labels, label_lens, canon=None, weights=None):
     of sum_b sum_q weights[b][q] * ctc[b][q] over the hypotheses with a finite score (rows past `lens` are zero).  Without weights only
     the forward sweeps run and only the class log-probabilities are allocated."""
     logits, lens_dev, labels, label_lens, n, stride, M, nbytes, squeeze = _labelling_args(
-        "ctc_nbest", "vocr_ctc_nbest_workspace_bytes",
+        "ctc_nbest", _lib.load().vocr_ctc_nbest_workspace_bytes,
         "2 <= V <= 256, n <= 128, label length <= 1823, B * n * 8 * T * (2 * label length + 1) bytes of lattices <= 2 GiB",
         logits, lens, labels, label_lens, canon)
     T, B, V = logits.shape
@@ -1495,14 +1487,17 @@ def ctc_entropy(logits, lens, labels, label_lens, canon=None, coeff=None):
     if labels.dim() != 2 or label_lens.dim() != 1:
         raise RuntimeError("ctc_entropy: labels must be int32 [B,L] and label_lens int32 [B] (labels %s, label_lens %s)"
                            % (tuple(labels.shape), tuple(label_lens.shape)))
-    logits, lens_dev, labels, label_lens, _, stride, M, _, _ = _labelling_args(
-        "ctc_entropy", "vocr_ctc_align_workspace_bytes", "2 <= V <= 256, T * B < 2^31", logits, lens, labels, label_lens, canon)
+    def workspace_bytes(T, B, V, n, M):
+        nbytes = _lib.load().vocr_ctc_entropy_workspace_bytes(T, B, V, M, 0 if coeff is None else 1)
+        if nbytes == 0:                                     # one labelling per line: this entry's text names no n
+            raise RuntimeError("ctc_entropy: unsupported shape (T=%d B=%d V=%d label length %d; 2 <= V <= 256, label length <= 1663, "
+                               "B * 16 * T * (2 * label length + 1) bytes of lattices <= 2 GiB)" % (T, B, V, M))
+        return nbytes
+
+    logits, lens_dev, labels, label_lens, _, stride, M, nbytes, _ = _labelling_args(
+        "ctc_entropy", workspace_bytes, None, logits, lens, labels, label_lens, canon)
     T, B, V = logits.shape
     dev = logits.device
-    nbytes = _lib.load().vocr_ctc_entropy_workspace_bytes(T, B, V, M, 0 if coeff is None else 1)
-    if nbytes == 0:
-        raise RuntimeError("ctc_entropy: unsupported shape (T=%d B=%d V=%d label length %d; 2 <= V <= 256, label length <= 1663, "
-                           "B * 16 * T * (2 * label length + 1) bytes of lattices <= 2 GiB)" % (T, B, V, M))
     dlogits = None
     if coeff is not None:
         _need_gpu(coeff)
@@ -1550,16 +1545,7 @@ def ctc_keyword_scores(logits, lens, queries, query_lens, query_flags=None, cano
         if query_flags.dtype != torch.int32 or tuple(query_flags.shape) != (Q,):
             raise RuntimeError("ctc_keyword_scores: query_flags must be int32 [Q]")
         query_flags = query_flags.contiguous()
-    if torch.is_tensor(lens):
-        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
-    if lens_dev.numel() != B:
-        raise RuntimeError("ctc_keyword_scores: %d lengths for %d lines" % (lens_dev.numel(), B))
-    if canon is not None:
-        _need_gpu(canon)
-        if canon.dtype != torch.int32 or canon.numel() != V:
-            raise RuntimeError("ctc_keyword_scores: canon must be int32 [V]")
+    lens_dev = _lens_canon("ctc_keyword_scores", logits, lens, canon)
     log_count = torch.empty(B, Q, dtype=torch.float32, device=dev)
     best = torch.empty(B, Q, dtype=torch.float32, device=dev)
     span = torch.empty(B, Q, 2, dtype=torch.int32, device=dev)
@@ -1607,16 +1593,7 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
         raise RuntimeError("ctc_grammar_scores: unsupported shape (T=%d B=%d V=%d G=%d max_states=%d max_arcs=%d; 2 <= V <= 256, "
                            "max_states >= 1, max_states + max_arcs <= %d, T * B * G < 2^31, with best paths T * B * G * (max_states + "
                            "max_arcs) * 4 bytes of back pointers <= 2 GiB)" % (T, B, V, G, ms, ma, GRAMMAR_CELLS_MAX))
-    if torch.is_tensor(lens):
-        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
-    if lens_dev.numel() != B:
-        raise RuntimeError("ctc_grammar_scores: %d lengths for %d lines" % (lens_dev.numel(), B))
-    if canon is not None:
-        _need_gpu(canon)
-        if canon.dtype != torch.int32 or canon.numel() != V:
-            raise RuntimeError("ctc_grammar_scores: canon must be int32 [V]")
+    lens_dev = _lens_canon("ctc_grammar_scores", logits, lens, canon)
     t = {k: gp[k].contiguous() for k in names}
     logp = torch.empty(B, G, dtype=torch.float32, device=dev)
     best = labels = out_lens = None
