@@ -621,7 +621,7 @@ int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens, int t, int
  * The excluded term is CTC's repeat rule: the same class twice in a row needs a blank between, the route through W.  It is evaluated as
  * lse(prefix, suffix) over the class-sorted incoming arcs, never as a subtraction.  For a DETERMINISTIC automaton every labelling has
  * one state sequence and P is exactly the probability that the labelling is accepted; for a non-deterministic one it is the sum over
- * (frame path, automaton path) pairs.  WHAT IT IS NOT: there are no weights on the arcs (no language model), no gradient, and the best
+ * (frame path, automaton path) pairs.  WHAT IT IS NOT: there are no weights on the arcs (no language model), and the best
  * score is the maximum over single PATHS through the product (frame path and automaton path), not the most probable accepted
  * labelling.  The best path is the same recursion with max, a back pointer per frame and cell in the workspace; a candidate replaces
  * the choice only when strictly greater - W: stay, then the incoming arcs in arc order; A: stay, then W[src], then the incoming arcs in
@@ -638,7 +638,7 @@ int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens, int t, int
  * in LDS; larger lexicons stay with vocr_ctc_word_beam_search), and with best paths t * b * g * (max_states + max_arcs) * 4 bytes of
  * back pointers <= 2 GiB.  Workspace (16-byte aligned: class log-probabilities, the plan, the back pointers when want_best) from
  * vocr_ctc_grammar_workspace_bytes (0 for an unsupported shape); bad arguments and unsupported shapes fail with VOCR_EINVAL before any
- * launch. */
+ * launch.  The gradient of ln P with respect to the logits: vocr_ctc_grammar_grad below. */
 size_t vocr_ctc_grammar_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_best);
 int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
                             const int32_t* g_state_off, const int32_t* g_arc_off, int g,
@@ -646,6 +646,43 @@ int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int
                             const int32_t* accept, int max_states, int max_arcs,
                             float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- grammar-constrained CTC training: the gradient of the match score (graph-based temporal classification) ---- */
+/* out_logp[b] = ln P(line b's labelling is accepted by automaton which[b]) and dlogits = d/dlogits sum_b weights[b] * ln P_b.  The
+ * automaton tables, their sort order (dst, class, src), classes, blank, the repeat rule and the validity rules are exactly those of
+ * vocr_ctc_grammar_scores; which[B] device int32 pairs line b with ONE automaton (several lines may share one): one workgroup per
+ * line, not per (line, automaton).  out_logp[b] holds the bits of vocr_ctc_grammar_scores' out_logp[b][which[b]] for the same
+ * tables, max_states and max_arcs, with or without weights (the same device code runs the forward sweep).
+ * With the cells c = W[s], A[a], e(c) the class a cell emits (blank for W, cls_a for A), alpha_t(c) the recursion above and
+ * bhat_t(c) = the log-sum over all accepted continuations that start in c at frame t, frame t's emission included:
+ *   t = len-1: bhat(W[s]) = lp_t(blank) if s accepts, bhat(A[a]) = lp_t(cls_a) if dst_a accepts, everything else -inf;
+ *   t < len-1: bhat(W[s]) = lp_t(blank) + lse(bhat'(W[s]), bhat'(A[a']) for every a' with src_a' = s);
+ *              bhat(A[a]) = lp_t(cls_a) + lse(bhat'(A[a]), bhat'(W[dst_a]), bhat'(A[a']) for every a' with src_a' = dst_a and
+ *                           class(cls_a') != class(cls_a))                                   (bhat' the row of frame t + 1)
+ * - the alpha recursion over the mirrored automaton (arcs (dst, cls, src) sorted by (src, class, dst), every accepting state a
+ * start) on the frames read backwards, and evaluated as that: the call sorts the arcs itself.
+ *   occ(t, k) = sum over the cells with e(c) = k of exp(alpha_t(c) + bhat_t(c) - lp_t(k) - ln P)            (sums to 1 over k)
+ *   dlogits[t][b][v] = w_b * p_t(v) * (occ(t, class(v)) / P_t(class(v)) - 1)                 (the form of vocr_ctc_nbest_grad)
+ * For a non-deterministic automaton the same formula is the gradient of the sum over (frame path, automaton path) pairs.
+ * THE FAMILY'S RULES: rows t >= lens[b] are zeros.  A line whose ln P = -inf, whose automaton breaks a rule or whose which[b] lies
+ * outside [0, g) gets out_logp = -inf and rows that are exactly zero whatever its weight; it poisons nothing else.  lens[b] = 0:
+ * 0 or -inf by the start state's accept flag, and zero rows.  -inf logits are legal: a column with p = 0 gets 0, and a class with
+ * P_t(c) = 0 never yields NaN or inf.  No floating-point atomics: the per-class occupancy sum runs over a class-sorted arc index built
+ * on the device, one wave per class, in a fixed order; results are bit-identical from run to run, and a line's rows depend on that
+ * line and its automaton alone.  weights (device fp32 [B]) and dlogits ([T][B][V]) are both NULL or both given; both NULL: scores
+ * only, nothing is stored and no backward sweep runs.  WHAT IT IS NOT: no weights on the arcs, no best path (vocr_ctc_grammar_scores
+ * has it), and the forward rows are STORED: t * b * (max_states + max_arcs) * 4 bytes of workspace, which must stay within 2 GiB -
+ * the caller cuts the batch (every line is independent).  Limits: those of vocr_ctc_grammar_scores (2 <= v <= 256, g >= 1,
+ * t * b * g < 2^31, max_states + max_arcs <= 8192) plus that lattice.  Workspace (16-byte aligned: class log-probabilities, the plan,
+ * and with want_grad the mirrored tables, their plan, the sort keys and the lattice) from vocr_ctc_grammar_grad_workspace_bytes (0
+ * for an unsupported shape); bad arguments and unsupported shapes fail with VOCR_EINVAL before any launch. */
+size_t vocr_ctc_grammar_grad_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad);
+int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                          const int32_t* g_state_off, const int32_t* g_arc_off, int g,
+                          const int32_t* arc_src, const int32_t* arc_cls, const int32_t* arc_dst,
+                          const int32_t* accept, int max_states, int max_arcs,
+                          const int32_t* which, const float* weights, float* out_logp, float* dlogits,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- edit statistics: compute_cer_wer of test_on_val (src/textutils.py:264-351, src/train_cnn_lstm.py:32-100) and src/edit_dist_trace.py ---- */
 /* Levenshtein statistics (unit costs) of np (hypothesis, reference) pairs that are already on the device: distances and lengths over

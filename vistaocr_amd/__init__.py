@@ -17,6 +17,7 @@ from .score import ErrorScorer, ErrorStats, OracleStats                         
 from .ctc import CTCLoss                                                                # noqa: F401,E402
 from .risk import MinErrorRateLoss                                                      # noqa: F401,E402
 from .entropy import EntropyRegularizedCTCLoss                                          # noqa: F401,E402
+from .grammar_loss import GrammarCTCLoss                                                # noqa: F401,E402
 from .decoder import ArgmaxDecoder, BeamDecoder, WordBeamDecoder                        # noqa: F401,E402
 from .lm import CharNgramLM, WordNgramLM                                                # noqa: F401,E402
 from .model import CnnOcrModel                                                          # noqa: F401,E402
@@ -24,6 +25,6 @@ from .train import FlatClampAdam, make_optimizer, seed_rank, train, train_async 
 from .dataset import OcrDataset                                                         # noqa: F401,E402
 from .augment import AugmentParams, DeviceAugmenter                                     # noqa: F401,E402
 
-__all__ = ["DeviceAugmenter", "AugmentParams","Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "EntropyRegularizedCTCLoss", "ArgmaxDecoder", "BeamDecoder",
+__all__ = ["DeviceAugmenter", "AugmentParams","Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "EntropyRegularizedCTCLoss", "GrammarCTCLoss", "ArgmaxDecoder", "BeamDecoder",
            "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "Grammar", "GrammarMatcher", "GrammarHits", "ErrorScorer", "ErrorStats", "OracleStats",
            "CnnOcrModel", "FlatClampAdam", "make_optimizer", "seed_rank", "train", "train_async", "OcrDataset"]

@@ -55,12 +55,14 @@ __device__ __forceinline__ int lower_bound(int lo, int hi, int want, Key key) {
 
 // grid.x = G, 256 threads.  flags[k] = 1 for an automaton that breaks a rule (nothing else is written for it).  st[k][s] = {first,
 // end} of the incoming arcs of s; meta[k][a] = {src, class column, xa, xb}: the other classes' incoming arcs of src are those before
-// xa (read: the exclusive prefix at xa; -1: none) and from xb on (the inclusive suffix at xb; -1: none).
+// xa (read: the exclusive prefix at xa; -1: none) and from xb on (the inclusive suffix at xb; -1: none).  arc_stride = 0: automaton k's
+// arcs lie at g_arc_off[k] of the arc arrays (the caller's tables); > 0: at k * arc_stride (the mirrored tables in the workspace).
 __global__ __launch_bounds__(256) void grammar_plan_kernel(const int32_t* __restrict__ canon, const int32_t* __restrict__ g_state_off,
                                                            const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_src,
                                                            const int32_t* __restrict__ arc_cls, const int32_t* __restrict__ arc_dst, int V,
-                                                           int max_states, int max_arcs, int32_t* __restrict__ flags,
-                                                           int2* __restrict__ st, int4* __restrict__ meta, int32_t* __restrict__ big_all) {
+                                                           int max_states, int max_arcs, int arc_stride,
+                                                           int32_t* __restrict__ flags, int2* __restrict__ st, int4* __restrict__ meta,
+                                                           int32_t* __restrict__ big_all) {
     __shared__ int s_wcnt[4];
     __shared__ int s_base;
     const int k = blockIdx.x, tid = threadIdx.x;
@@ -71,9 +73,10 @@ __global__ __launch_bounds__(256) void grammar_plan_kernel(const int32_t* __rest
         return;
     }
     const int S = (int)S_, E = (int)E_;
-    const int32_t* src = arc_src + a0;
-    const int32_t* cls = arc_cls + a0;
-    const int32_t* dst = arc_dst + a0;
+    const long base = arc_stride ? (long)k * arc_stride : (long)a0;
+    const int32_t* src = arc_src + base;
+    const int32_t* cls = arc_cls + base;
+    const int32_t* dst = arc_dst + base;
     auto cls_of = [&](int i) { return class_of(canon, min(max(cls[i], 0), V - 1)); };
     int bad = 0;
     for (int i = tid; i < E; i += 256) {
@@ -241,6 +244,142 @@ __device__ __forceinline__ void wave_scan(const float* __restrict__ A, float* __
     }
 }
 
+// What a sweep reads of one automaton: the plan kernel's tables (in global memory, or staged in LDS)
+struct GView {
+    int S, N;
+    const int2* st;
+    const int4* meta;
+    const int32_t* bigs;
+    int nbig;
+};
+
+// the plan of automaton k as the plan kernel wrote it
+__device__ __forceinline__ GView g_view(int k, int S, int E, const int2* __restrict__ st_all, const int4* __restrict__ meta_all,
+                                        const int32_t* __restrict__ big_all, int max_states, int max_arcs) {
+    const int32_t* bigs = big_all + (long)k * big_stride(max_arcs);
+    return {S, S + E, st_all + (long)k * max_states, meta_all + (long)k * max_arcs, bigs + 1, bigs[0]};
+}
+
+// ... copied into LDS at `at` (the caller's threads are past every read of what lay there); ends with a barrier
+__device__ __forceinline__ GView g_stage(const GView& g, float* at, int max_states, int max_arcs, int tid, int NT) {
+    int4* lm = reinterpret_cast<int4*>(at);
+    int2* ls = reinterpret_cast<int2*>(lm + max_arcs);
+    int32_t* lb = reinterpret_cast<int32_t*>(ls + max_states);
+    for (int i = tid; i < g.N - g.S; i += NT) lm[i] = g.meta[i];
+    for (int i = tid; i < g.S; i += NT) ls[i] = g.st[i];
+    for (int i = tid; i < g.nbig; i += NT) lb[i] = g.bigs[i];
+    __syncthreads();
+    return {g.S, g.N, ls, lm, lb, g.nbig};
+}
+
+// The first frame's row from its class log-probabilities lpr (in LDS): the W cell of every start state and the arc cells that leave
+// one.  start = NULL: state 0 alone (the forward sweep); else start[s] != 0 (the mirrored sweep: every accepting state).
+__device__ __forceinline__ void g_first_row(const GView& g, float* __restrict__ row, const float* __restrict__ lpr,
+                                            const int32_t* __restrict__ start, int tid, int NT) {
+    for (int c = tid; c < g.N; c += NT) {
+        float v = NEG_INF;
+        if (c < g.S) {
+            if (start ? start[c] != 0 : c == 0) v = lpr[0];
+        } else {
+            const int4 m = g.meta[c - g.S];
+            if (start ? start[m.x] != 0 : m.x == 0) v = lpr[m.y];
+        }
+        row[c] = v;
+    }
+    __syncthreads();
+}
+
+// One frame of the recursion: row `nxt` from row `cur`, the frame's class log-probabilities read from lp_row (global) into lpr (LDS)
+// on the way.  bp_row (max pass): where each cell came from.  Ends with a barrier: nxt, and lpr, are complete.
+template <bool BEST>
+__device__ __forceinline__ void g_step(const GView& g, const float* __restrict__ cur, float* __restrict__ nxt, float* __restrict__ pre,
+                                       float* __restrict__ suf, float* __restrict__ lpr, const float* __restrict__ lp_row, int V,
+                                       int32_t* __restrict__ bp_row, int tid, int NT, int lane, int wave) {
+    const int S = g.S, N = g.N;
+    const float* A = cur + S;
+    const float next_lp = tid < V ? lp_row[tid] : 0.f;             // this frame's row: in LDS after phase 1
+    // phase 1: the scans of every state's incoming arcs
+    for (int s = tid; s < S; s += NT) {
+        const int2 io = g.st[s];
+        const int D = io.y - io.x;
+        if (D > 0 && D < WAVE_DEG) lane_scan<BEST>(A, pre, suf, io.x, io.y);
+    }
+    for (int kb = wave; kb < g.nbig; kb += NT >> 6) {              // the states of many incoming arcs, dealt out to the waves
+        const int2 io = g.st[g.bigs[kb]];
+        wave_scan<BEST>(A, pre, suf, __builtin_amdgcn_readfirstlane(io.x), __builtin_amdgcn_readfirstlane(io.y), lane);
+    }
+    if (tid < V) lpr[tid] = next_lp;
+    __syncthreads();
+    // phase 2: every cell
+    for (int c = tid; c < N; c += NT) {
+        float v;
+        int from = c;
+        if (c < S) {
+            const int2 io = g.st[c];
+            int arc;
+            const float inc = g_read<BEST>(suf, io.y > io.x ? io.x : -1, A, arc);
+            const float w = cur[c];
+            if (BEST) {
+                v = w;
+                if (inc > v) { v = inc; from = S + arc; }
+            } else {
+                v = lse2(w, inc);
+            }
+            v += lpr[0];
+        } else {
+            const int4 m = g.meta[c - S];
+            int arc_a, arc_b;
+            const float self = cur[c], w = cur[m.x];
+            const float pa = g_read<BEST>(pre, m.z, A, arc_a), pb = g_read<BEST>(suf, m.w, A, arc_b);
+            if (BEST) {
+                v = self;
+                if (w > v) { v = w; from = m.x; }
+                if (pa > v) { v = pa; from = S + arc_a; }
+                if (pb > v) { v = pb; from = S + arc_b; }
+            } else {
+                const float mx = fmaxf(fmaxf(self, w), fmaxf(pa, pb));
+                v = mx == NEG_INF ? NEG_INF : logf(expf(self - mx) + expf(w - mx) + expf(pa - mx) + expf(pb - mx)) + mx;
+            }
+            v += lpr[m.y];
+        }
+        nxt[c] = v;
+        if (BEST) bp_row[c] = from;
+    }
+    __syncthreads();
+}
+
+// The end: the accepting W cells in state order, then the arc cells with an accepting destination in arc order, joined over the
+// workgroup in r_m / r_s / r_i [NT]; the result is their entry 0 (after the last barrier).  len = 0: the start state's flag.
+template <bool BEST>
+__device__ __forceinline__ void g_finish(const GView& g, const float* __restrict__ cur, int len, const int32_t* __restrict__ acc_s,
+                                         const int32_t* __restrict__ dst, float* r_m, float* r_s, int* r_i, int tid, int NT) {
+    GAcc acc = g_none();
+    if (len > 0) {
+        for (int c = tid; c < g.N; c += NT) {
+            const bool fin = c < g.S ? acc_s[c] != 0 : acc_s[dst[c - g.S]] != 0;
+            if (fin) acc = g_join<BEST>(acc, g_elem(cur[c], c));
+        }
+    } else if (tid == 0 && acc_s[0] != 0) {
+        acc = g_elem(0.f, 0);
+    }
+    r_m[tid] = acc.m;
+    r_s[tid] = acc.s;
+    r_i[tid] = acc.i;
+    __syncthreads();
+    for (int o = NT >> 1; o > 0; o >>= 1) {
+        if (tid < o) {
+            const GAcc l = {r_m[tid], r_s[tid], r_i[tid]}, r = {r_m[tid + o], r_s[tid + o], r_i[tid + o]};
+            GAcc j;
+            if (BEST) j = (r.m > l.m || (r.m == l.m && r.i >= 0 && (l.i < 0 || r.i < l.i))) ? r : l;   // the lower cell wins a tie
+            else j = g_join<false>(l, r);
+            r_m[tid] = j.m;
+            r_s[tid] = j.s;
+            r_i[tid] = j.i;
+        }
+        __syncthreads();
+    }
+}
+
 // grid.x = B * G, NT_SMALL or NT_BIG threads, dynamic LDS: two rows of maxN cells (states, then arcs), the two scans (maxN words
 // each, only E used) and two staged rows of class log-probabilities.  out: out_logp (sum pass) or out_best (max pass).
 template <bool BEST>
@@ -274,23 +413,10 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __rest
     const int S = g_state_off[k + 1] - g_state_off[k], E = g_arc_off[k + 1] - g_arc_off[k], N = S + E;
     const int32_t* acc_s = accept + g_state_off[k];
     const int32_t* dst = arc_dst + g_arc_off[k];
-    const int2* st = st_all + (long)k * max_states;
-    const int4* meta = meta_all + (long)k * max_arcs;
-    const int32_t* bigs = big_all + (long)k * big_stride(max_arcs);
-    const int nbig = *bigs++;
     const int len = min(max(lens[b], 0), T);
-    if (stage) {                                                   // the plan of this automaton in LDS: every frame reads all of it
-        int4* lm = reinterpret_cast<int4*>(sm + 4 * maxN + 2 * VMAX);
-        int2* ls = reinterpret_cast<int2*>(lm + max_arcs);
-        int32_t* lb = reinterpret_cast<int32_t*>(ls + max_states);
-        for (int i = tid; i < E; i += NT) lm[i] = meta[i];
-        for (int i = tid; i < S; i += NT) ls[i] = st[i];
-        for (int i = tid; i < nbig; i += NT) lb[i] = bigs[i];
-        meta = lm;
-        st = ls;
-        bigs = lb;
-        __syncthreads();
-    }
+    GView gv = g_view(k, S, E, st_all, meta_all, big_all, max_states, max_arcs);
+    if (stage) gv = g_stage(gv, sm + 4 * maxN + 2 * VMAX, max_states, max_arcs, tid, NT);   // every frame reads all of the plan
+    const int4* meta = gv.meta;
     float* row0 = sm;
     float* row1 = sm + maxN;
     float* pre = sm + 2 * maxN;
@@ -303,102 +429,18 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __rest
     if (len > 0) {
         if (tid < V) lprow[tid] = lpb[tid];
         __syncthreads();
-        for (int c = tid; c < N; c += NT) {
-            float v = NEG_INF;
-            if (c == 0) v = lprow[0];
-            else if (c >= S) {
-                const int4 m = meta[c - S];
-                if (m.x == 0) v = lprow[m.y];
-            }
-            row0[c] = v;
-        }
-        __syncthreads();
+        g_first_row(gv, row0, lprow, nullptr, tid, NT);
     }
     float* cur = row0;
     float* nxt = row1;
     for (int t = 1; t < len; ++t) {
-        const float* A = cur + S;
-        const float next_lp = tid < V ? lpb[t * tstride + tid] : 0.f;          // this frame's row: in LDS after phase 1
-        // phase 1: the scans of every state's incoming arcs
-        for (int s = tid; s < S; s += NT) {
-            const int2 io = st[s];
-            const int D = io.y - io.x;
-            if (D > 0 && D < WAVE_DEG) lane_scan<BEST>(A, pre, suf, io.x, io.y);
-        }
-        for (int kb = wave; kb < nbig; kb += NT >> 6) {            // the states of many incoming arcs, dealt out to the waves
-            const int2 io = st[bigs[kb]];
-            wave_scan<BEST>(A, pre, suf, __builtin_amdgcn_readfirstlane(io.x), __builtin_amdgcn_readfirstlane(io.y), lane);
-        }
-        float* lpr = lprow + (t & 1) * VMAX;
-        if (tid < V) lpr[tid] = next_lp;
-        __syncthreads();
-        // phase 2: every cell
-        for (int c = tid; c < N; c += NT) {
-            float v;
-            int from = c;
-            if (c < S) {
-                const int2 io = st[c];
-                int arc;
-                const float inc = g_read<BEST>(suf, io.y > io.x ? io.x : -1, A, arc);
-                const float w = cur[c];
-                if (BEST) {
-                    v = w;
-                    if (inc > v) { v = inc; from = S + arc; }
-                } else {
-                    v = lse2(w, inc);
-                }
-                v += lpr[0];
-            } else {
-                const int4 m = meta[c - S];
-                int arc_a, arc_b;
-                const float self = cur[c], w = cur[m.x];
-                const float pa = g_read<BEST>(pre, m.z, A, arc_a), pb = g_read<BEST>(suf, m.w, A, arc_b);
-                if (BEST) {
-                    v = self;
-                    if (w > v) { v = w; from = m.x; }
-                    if (pa > v) { v = pa; from = S + arc_a; }
-                    if (pb > v) { v = pb; from = S + arc_b; }
-                } else {
-                    const float mx = fmaxf(fmaxf(self, w), fmaxf(pa, pb));
-                    v = mx == NEG_INF ? NEG_INF : logf(expf(self - mx) + expf(w - mx) + expf(pa - mx) + expf(pb - mx)) + mx;
-                }
-                v += lpr[m.y];
-            }
-            nxt[c] = v;
-            if (BEST) bp[(long)t * N + c] = from;
-        }
-        __syncthreads();
+        g_step<BEST>(gv, cur, nxt, pre, suf, lprow + (t & 1) * VMAX, lpb + t * tstride, V, BEST ? bp + (long)t * N : nullptr, tid, NT, lane,
+                     wave);
         float* sw = cur;
         cur = nxt;
         nxt = sw;
     }
-
-    // the end: accepting W cells in state order, then arc cells with an accepting destination in arc order
-    GAcc acc = g_none();
-    if (len > 0) {
-        for (int c = tid; c < N; c += NT) {
-            const bool fin = c < S ? acc_s[c] != 0 : acc_s[dst[c - S]] != 0;
-            if (fin) acc = g_join<BEST>(acc, g_elem(cur[c], c));
-        }
-    } else if (tid == 0 && acc_s[0] != 0) {
-        acc = g_elem(0.f, 0);
-    }
-    r_m[tid] = acc.m;
-    r_s[tid] = acc.s;
-    r_i[tid] = acc.i;
-    __syncthreads();
-    for (int o = NT >> 1; o > 0; o >>= 1) {
-        if (tid < o) {
-            const GAcc l = {r_m[tid], r_s[tid], r_i[tid]}, r = {r_m[tid + o], r_s[tid + o], r_i[tid + o]};
-            GAcc j;
-            if (BEST) j = (r.m > l.m || (r.m == l.m && r.i >= 0 && (l.i < 0 || r.i < l.i))) ? r : l;   // the lower cell wins a tie
-            else j = g_join<false>(l, r);
-            r_m[tid] = j.m;
-            r_s[tid] = j.s;
-            r_i[tid] = j.i;
-        }
-        __syncthreads();
-    }
+    g_finish<BEST>(gv, cur, len, acc_s, dst, r_m, r_s, r_i, tid, NT);
     if (!BEST) {
         if (tid == 0) out[blk] = g_value({r_m[0], r_s[0], -1});
         return;
@@ -507,8 +549,8 @@ extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens,
     int32_t* bigs = (int32_t*)((char*)meta + p.meta_bytes);
     int32_t* bp = (int32_t*)((char*)bigs + p.big_bytes);
     if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
-    grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, flags, st, meta,
-                                          bigs);
+    grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, 0, flags, st,
+                                          meta, bigs);
     VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(plan)");
     ctc_grammar_kernel<false><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs, p.stage, t, b,
                                                              v, g, max_states, max_arcs, out_logp, nullptr, nullptr, nullptr, 0);
@@ -517,6 +559,379 @@ extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens,
         ctc_grammar_kernel<true><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs, p.stage, t,
                                                                 b, v, g, max_states, max_arcs, out_best, bp, out_labels, out_lens, label_stride);
         VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(max)");
+    }
+    return VOCR_OK;
+}
+
+// ---- vocr_ctc_grammar_grad: ln P of line b under automaton which[b], and its gradient with respect to the logits ----
+// The product graph is symmetric under reversal: bhat_t(c), the log-sum over the accepted continuations that start in cell c at frame t
+// (frame t's emission included), is the SAME recursion (g_first_row, g_step) over the mirrored automaton - arcs (dst, cls, src), sorted
+// by (src, class, dst), every accepting state a start - on the frames read backwards.
+//   kernel M  mirror   : one workgroup per automaton sorts its arcs by (src, class, dst, arc) - a bitonic sort of 64-bit keys in the
+//                        workspace - and writes the mirrored tables and perm[r] = the arc behind mirrored arc r; then sorts the mirrored
+//                        arcs by (class, r): cpos[r] = r's place in that order, cbeg[k] = where class k begins in it.
+//                        grammar_plan_kernel runs on the result.
+//   kernel G  sweep    : one workgroup per LINE.  Forward: ctc_grammar_kernel<false>'s frame loop and end, every row also stored
+//                        [len][maxN] in the workspace.  Backward: per frame the bhat row, then z(c) = exp(alpha + bhat - lp - ln P)
+//                        into LDS in class-sorted order (the words of the prefix scan, free between two steps), occ(k) = the sum
+//                        over class k's slots by one wave per class (lanes stride, then a butterfly: a fixed order), left in the
+//                        line's row of dlogits.  No beta lattice is stored, and no load from global memory is on the frame loop's
+//                        critical path: the cells' tables are in registers, the forward row is loaded ahead of the step.
+//   kernel R  rows     : one wave per row turns the occupancies into dlogits in vocr_ctc_nbest_grad's form.
+namespace {
+
+constexpr int IDX_BITS = 13;                 // GN_MAX = 2^13: a state or an arc index
+constexpr int IDX_MASK = (1 << IDX_BITS) - 1;
+constexpr size_t LATTICE_MAX_BYTES = (size_t)1 << 31;
+constexpr int CPT = GN_MAX / NT_BIG;         // cells a thread of the gradient sweep owns at most: N_SMALL / NT_SMALL is the same 8
+static_assert(CPT * NT_SMALL >= N_SMALL && CPT * NT_BIG >= GN_MAX, "a thread's cells");
+
+// ascending bitonic sort of p2 (a power of two) keys in global memory by one workgroup; ends with a barrier
+__device__ __forceinline__ void g_sort(unsigned long long* keys, int p2, int tid, int NT) {
+    for (int k2 = 2; k2 <= p2; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < p2; i += NT) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long a = keys[i], b = keys[l];
+                    if ((a > b) == ((i & k2) == 0)) {
+                        keys[i] = b;
+                        keys[l] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// grid.x = G.  Nothing is written for an automaton whose offsets break a rule (the plan kernel flags it from the same test); one
+// that breaks another rule gets tables that stay within bounds and are never swept.
+__global__ __launch_bounds__(NT_BIG) void grammar_mirror_kernel(const int32_t* __restrict__ canon, const int32_t* __restrict__ g_state_off,
+                                                                const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_src,
+                                                                const int32_t* __restrict__ arc_cls, const int32_t* __restrict__ arc_dst,
+                                                                int V, int max_states, int max_arcs, int p2max,
+                                                                unsigned long long* keys_all, int32_t* m_src, int32_t* m_cls,
+                                                                int32_t* m_dst, int32_t* perm_all, int32_t* cpos_all, int32_t* cbeg_all) {
+    const int k = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+    const int s0 = g_state_off[k], a0 = g_arc_off[k];
+    const long S_ = (long)g_state_off[k + 1] - s0, E_ = (long)g_arc_off[k + 1] - a0;
+    if (s0 < 0 || a0 < 0 || S_ < 1 || S_ > max_states || E_ < 0 || E_ > max_arcs) return;
+    const int E = (int)E_;
+    const int32_t* src = arc_src + a0;
+    const int32_t* cls = arc_cls + a0;
+    const int32_t* dst = arc_dst + a0;
+    unsigned long long* keys = keys_all + (long)k * p2max;
+    int32_t* ms = m_src + (long)k * max_arcs;
+    int32_t* mc = m_cls + (long)k * max_arcs;
+    int32_t* md = m_dst + (long)k * max_arcs;
+    int32_t* perm = perm_all + (long)k * max_arcs;
+    int32_t* cpos = cpos_all + (long)k * max_arcs;
+    int32_t* cbeg = cbeg_all + (long)k * (VMAX + 1);
+    int p2 = 1;
+    while (p2 < E) p2 <<= 1;                                       // <= p2max: E <= max_arcs
+    for (int i = tid; i < p2; i += NT) {
+        unsigned long long key = ~0ull;
+        if (i < E) {
+            const unsigned long long c = (unsigned long long)class_of(canon, min(max(cls[i], 0), V - 1));
+            key = ((unsigned long long)(src[i] & IDX_MASK) << (2 * IDX_BITS + 8)) | (c << (2 * IDX_BITS)) |
+                  ((unsigned long long)(dst[i] & IDX_MASK) << IDX_BITS) | (unsigned long long)i;
+        }
+        keys[i] = key;
+    }
+    __syncthreads();
+    g_sort(keys, p2, tid, NT);
+    for (int r = tid; r < E; r += NT) {
+        const int i = (int)(keys[r] & IDX_MASK);
+        ms[r] = dst[i];
+        mc[r] = cls[i];
+        md[r] = src[i];
+        perm[r] = i;
+    }
+    __syncthreads();
+    for (int r = tid; r < p2; r += NT) {
+        unsigned long long key = ~0ull;
+        if (r < E) key = ((unsigned long long)class_of(canon, min(max(mc[r], 0), V - 1)) << IDX_BITS) | (unsigned long long)r;
+        keys[r] = key;
+    }
+    __syncthreads();
+    g_sort(keys, p2, tid, NT);
+    __syncthreads();                                               // (a single key is not sorted: no barrier in there)
+    for (int j = tid; j < E; j += NT) cpos[(int)(keys[j] & IDX_MASK)] = j;
+    auto cls_key = [&](int j) { return (int)(keys[j] >> IDX_BITS); };
+    for (int c = tid; c <= V; c += NT) cbeg[c] = lower_bound(0, E, c, cls_key);
+}
+
+// rows [t0, T) of line b as zeros
+__device__ __forceinline__ void g_zero_rows(float* __restrict__ dlogits, int b, int t0, int T, int B, int V, int tid, int NT) {
+    for (long i = tid; i < (long)(T - t0) * V; i += NT) {
+        const long t = t0 + i / V;
+        dlogits[(t * B + b) * V + i % V] = 0.f;
+    }
+}
+
+// grid.x = B, NT_SMALL or NT_BIG threads, ctc_grammar_kernel's dynamic LDS.  dlogits = NULL: scores only (lat and the mirrored
+// plan are not touched); else the rows of a line with a score hold occ(t, k) behind it, every other row zeros.
+__global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
+    const float* __restrict__ clp, const int32_t* __restrict__ lens, const int32_t* __restrict__ g_state_off, const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_dst,
+    const int32_t* __restrict__ accept, const int32_t* __restrict__ which,
+    const int32_t* __restrict__ flags_f, const int2* __restrict__ st_f, const int4* __restrict__ meta_f, const int32_t* __restrict__ big_f,
+    const int32_t* __restrict__ flags_m, const int2* __restrict__ st_m, const int4* __restrict__ meta_m, const int32_t* __restrict__ big_m,
+    const int32_t* __restrict__ perm_all, const int32_t* __restrict__ cpos_all, const int32_t* __restrict__ cbeg_all, int stage, int T,
+    int B, int V, int G, int max_states, int max_arcs, float* __restrict__ out_logp, float* __restrict__ lat, float* __restrict__ dlogits) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float r_m[NT_BIG];
+    __shared__ float r_s[NT_BIG];
+    __shared__ int r_i[NT_BIG];
+    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, k = which[b];
+    const int maxN = max_states + max_arcs;
+    bool bad = k < 0 || k >= G;
+    if (!bad) bad = flags_f[k] != 0 || (dlogits && flags_m[k] != 0);
+    if (bad) {                                                     // poisons its own line alone
+        if (tid == 0) out_logp[b] = NEG_INF;
+        if (dlogits) g_zero_rows(dlogits, b, 0, T, B, V, tid, NT);
+        return;
+    }
+    const int S = g_state_off[k + 1] - g_state_off[k], E = g_arc_off[k + 1] - g_arc_off[k], N = S + E;
+    const int32_t* acc_s = accept + g_state_off[k];
+    const int32_t* dst = arc_dst + g_arc_off[k];
+    const int len = min(max(lens[b], 0), T);
+    float* stage_at = sm + 4 * maxN + 2 * VMAX;
+    GView gv = g_view(k, S, E, st_f, meta_f, big_f, max_states, max_arcs);
+    if (stage) gv = g_stage(gv, stage_at, max_states, max_arcs, tid, NT);
+    float* row0 = sm;
+    float* row1 = sm + maxN;
+    float* pre = sm + 2 * maxN;
+    float* suf = sm + 3 * maxN;
+    float* lprow = sm + 4 * maxN;                                  // [2][VMAX]
+    const long tstride = (long)B * V;
+    const float* lpb = clp + (long)b * V;
+    float* lat_b = dlogits ? lat + (long)b * T * maxN : nullptr;   // [len][maxN]: the forward rows
+
+    // forward: ctc_grammar_kernel<false>, frame for frame
+    if (len > 0) {
+        if (tid < V) lprow[tid] = lpb[tid];
+        __syncthreads();
+        g_first_row(gv, row0, lprow, nullptr, tid, NT);
+        if (lat_b)
+            for (int c = tid; c < N; c += NT) lat_b[c] = row0[c];
+    }
+    float* cur = row0;
+    float* nxt = row1;
+    for (int t = 1; t < len; ++t) {
+        g_step<false>(gv, cur, nxt, pre, suf, lprow + (t & 1) * VMAX, lpb + t * tstride, V, nullptr, tid, NT, lane, wave);
+        float* sw = cur;
+        cur = nxt;
+        nxt = sw;
+        if (lat_b)
+            for (int c = tid; c < N; c += NT) lat_b[(long)t * maxN + c] = cur[c];
+    }
+    g_finish<false>(gv, cur, len, acc_s, dst, r_m, r_s, r_i, tid, NT);
+    const float lnP = g_value({r_m[0], r_s[0], -1});
+    if (tid == 0) out_logp[b] = lnP;
+    if (!dlogits) return;
+    if (lnP == NEG_INF || len == 0) {
+        g_zero_rows(dlogits, b, 0, T, B, V, tid, NT);
+        return;
+    }
+    __syncthreads();                                               // every thread has read ln P: the reduction's arrays are free
+    int* cb = reinterpret_cast<int*>(r_m);                         // [V + 1]: where class k begins among the class-sorted arc cells
+    const int32_t* cbeg = cbeg_all + (long)k * (VMAX + 1);
+    for (int i = tid; i <= V; i += NT) cb[i] = cbeg[i];
+
+    // backward: the same recursion over the mirrored automaton (the forward's staged plan is dead by now), the occupancy folded in.
+    // Nothing in the frame loop waits for global memory: what a thread needs of its cells c = tid + i NT (at most CPT of them:
+    // N <= CPT * NT at both thread counts) is in registers before it starts, and the forward row of frame t is loaded ahead of
+    // the step that makes frame t's bhat.
+    gv = g_view(k, S, E, st_m, meta_m, big_m, max_states, max_arcs);
+    if (stage) gv = g_stage(gv, stage_at, max_states, max_arcs, tid, NT);
+    const int32_t* perm = perm_all + (long)k * max_arcs;
+    const int32_t* cpos = cpos_all + (long)k * max_arcs;
+    int ai[CPT], zi[CPT], ecol[CPT];                               // the cell's word in a forward row, its slot among the class-sorted z, its class
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+        const int c = tid + i * NT;
+        ai[i] = -1;
+        zi[i] = ecol[i] = 0;
+        if (c < S) {
+            ai[i] = zi[i] = c;
+        } else if (c < N) {
+            ai[i] = S + perm[c - S];
+            zi[i] = S + cpos[c - S];
+            ecol[i] = gv.meta[c - S].y;
+        }
+    }
+    if (tid < V) lprow[tid] = lpb[(long)(len - 1) * tstride + tid];
+    __syncthreads();
+    g_first_row(gv, row0, lprow, acc_s, tid, NT);
+    cur = row0;
+    nxt = row1;
+    for (int j = 0; j < len; ++j) {
+        const int t = len - 1 - j;
+        const float* lpr = lprow + (j & 1) * VMAX;
+        const float* al = lat_b + (long)t * maxN;
+        float a[CPT];
+#pragma unroll
+        for (int i = 0; i < CPT; ++i) a[i] = ai[i] >= 0 ? al[ai[i]] : NEG_INF;
+        if (j > 0) {
+            g_step<false>(gv, cur, nxt, pre, suf, lprow + (j & 1) * VMAX, lpb + t * tstride, V, nullptr, tid, NT, lane, wave);
+            float* sw = cur;
+            cur = nxt;
+            nxt = sw;
+        }
+#pragma unroll
+        for (int i = 0; i < CPT; ++i) {                            // z(c): the share of the accepted mass that passes through c at t
+            if (ai[i] < 0) continue;
+            const float bh = cur[tid + i * NT];
+            pre[zi[i]] = (a[i] == NEG_INF || bh == NEG_INF) ? 0.f : expf(a[i] + bh - lpr[ecol[i]] - lnP);
+        }
+        __syncthreads();
+        float* occ_row = dlogits + ((long)t * B + b) * V;          // occ(t, k) waits here for the row kernel
+        for (int kc = wave; kc < V; kc += NT >> 6) {               // one wave per class over its slots, a fixed order
+            const int q0 = kc == 0 ? 0 : S + cb[kc], q1 = kc == 0 ? S : S + cb[kc + 1];
+            float s = 0.f;
+            for (int q = q0 + lane; q < q1; q += 64) s += pre[q];
+            s = wave_sum(s);
+            if (lane == 0) occ_row[kc] = s;
+        }
+        __syncthreads();                                           // the next step's scans write pre
+    }
+    g_zero_rows(dlogits, b, len, T, B, V, tid, NT);
+}
+
+// grid.x = ceil(T B / 4), 256 threads: one wave per row (t, b) turns the row of class occupancies the sweep left in dlogits into the
+// row of the gradient, share * (w occ) - p w, in ctc_grad_rows' arithmetic.  Rows the sweep wrote as zeros are left alone.
+__global__ __launch_bounds__(256) void grammar_grad_rows_kernel(const float* __restrict__ logits, const float* __restrict__ clp,
+                                                                const int32_t* __restrict__ lens, const int32_t* __restrict__ canon,
+                                                                const float* __restrict__ weights, const float* __restrict__ out_logp,
+                                                                int T, int B, int V, float* __restrict__ dlogits) {
+    __shared__ float s_occ[4][VMAX];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + wave;
+    if (row >= (long)T * B) return;
+    const int t = (int)(row / B), b = (int)(row - (long)t * B);
+    if (t >= min(max(lens[b], 0), T) || out_logp[b] == NEG_INF) return;
+    float* out = dlogits + row * V;
+    float* occ = s_occ[wave];
+    for (int v = lane; v < V; v += 64) occ[v] = out[v];
+    __builtin_amdgcn_wave_barrier();
+    const float* xr = logits + row * V;
+    const float* cr = clp + row * V;
+    const float w = weights[b];
+    const RowLse rl = wave_row_lse(xr, V, lane);                   // the bits of class_logprob_rows_kernel's log-softmax
+    for (int v = lane; v < V; v += 64) {
+        const float lpv = row_logprob(rl, xr, v);
+        const float share = (lpv == NEG_INF) ? 0.f : expf(lpv - cr[v]);          // p_t(v) / P_t(class(v))
+        out[v] = share * (w * occ[class_of(canon, v)]) - expf(lpv) * w;
+    }
+}
+
+struct GradPlan {
+    Plan p;
+    int p2;                // one automaton's sort keys: max_arcs rounded up to a power of two
+    size_t arcs_bytes, keys_bytes, cbeg_bytes, lattice_bytes;
+    bool ok;
+    size_t mirror_bytes() const { return 5 * arcs_bytes + keys_bytes + cbeg_bytes + p.plan_bytes(); }
+};
+
+GradPlan grad_plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad) {
+    GradPlan q = {plan_for(t, b, v, g, max_states, max_arcs, 0), 1, 0, 0, 0, 0, false};
+    if (!q.p.ok) return q;
+    q.ok = true;
+    if (!want_grad) return q;
+    while (q.p2 < max_arcs) q.p2 <<= 1;
+    q.arcs_bytes = align16((size_t)g * max_arcs * sizeof(int32_t));
+    q.keys_bytes = align16((size_t)g * q.p2 * sizeof(unsigned long long));
+    q.cbeg_bytes = align16((size_t)g * (VMAX + 1) * sizeof(int32_t));
+    q.lattice_bytes = (size_t)t * b * ((size_t)max_states + max_arcs) * sizeof(float);
+    if (q.lattice_bytes > LATTICE_MAX_BYTES) q.ok = false;
+    q.lattice_bytes = align16(q.lattice_bytes);
+    return q;
+}
+
+}  // namespace
+
+extern "C" size_t vocr_ctc_grammar_grad_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad) {
+    const GradPlan q = grad_plan_for(t, b, v, g, max_states, max_arcs, want_grad);
+    if (!q.ok) return 0;
+    return clp_bytes(t, b, v) + q.p.plan_bytes() + (want_grad ? q.mirror_bytes() + q.lattice_bytes : 0);
+}
+
+extern "C" int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                     const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
+                                     const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, int max_states, int max_arcs,
+                                     const int32_t* which, const float* weights, float* out_logp, float* dlogits, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    const char* who = "vocr_ctc_grammar_grad";
+    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "%s: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", who, VMAX, t, b, v);
+    VOCR_CHECK_ARG(g >= 1, "%s: need g >= 1 (g=%d)", who, g);
+    VOCR_CHECK_ARG(max_states >= 1 && max_arcs >= 0 && (long)max_states + max_arcs <= GN_MAX,
+                   "%s: need max_states >= 1, max_arcs >= 0 and max_states + max_arcs <= %d (max_states=%d max_arcs=%d)", who, GN_MAX,
+                   max_states, max_arcs);
+    VOCR_CHECK_ARG(!weights == !dlogits, "%s: weights and dlogits go together (weights %s, dlogits %s)", who, weights ? "given" : "NULL",
+                   dlogits ? "given" : "NULL");
+    const int want_grad = dlogits ? 1 : 0;
+    const GradPlan q = grad_plan_for(t, b, v, g, max_states, max_arcs, want_grad);
+    VOCR_CHECK_ARG(q.ok, "%s: unsupported shape (t=%d b=%d v=%d g=%d max_states=%d max_arcs=%d): t*b*g must stay below 2^31 and the stored "
+                   "lattice, t*b*(max_states+max_arcs)*4 bytes, within 2 GiB", who, t, b, v, g, max_states, max_arcs);
+    VOCR_CHECK_ARG(logits && lens && g_state_off && g_arc_off && accept && which && out_logp && workspace &&
+                   (max_arcs == 0 || (arc_src && arc_cls && arc_dst)), "%s: null pointer", who);
+    const size_t need = clp_bytes(t, b, v) + q.p.plan_bytes() + (want_grad ? q.mirror_bytes() + q.lattice_bytes : 0);
+    VOCR_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    VOCR_CHECK_ARG((((uintptr_t)workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    static VocrPerDevice lds_set;
+    const void* const big[] = {(const void*)ctc_grammar_grad_kernel};
+    if (vocr_allow_dynamic_lds(big, 1, (int)LDS_DYN_MAX, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
+    const Plan& p = q.p;
+    char* at = (char*)workspace;
+    auto take = [&](size_t bytes) {
+        char* r = at;
+        at += bytes;
+        return r;
+    };
+    float* clp = (float*)take(clp_bytes(t, b, v));
+    int32_t* flags = (int32_t*)take(p.flags_bytes);
+    int2* st = (int2*)take(p.st_bytes);
+    int4* meta = (int4*)take(p.meta_bytes);
+    int32_t* bigs = (int32_t*)take(p.big_bytes);
+    if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
+    grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, 0, flags, st,
+                                          meta, bigs);
+    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(plan)");
+    int32_t *flags_m = nullptr, *bigs_m = nullptr, *perm = nullptr, *cpos = nullptr, *cbeg = nullptr;
+    int2* st_m = nullptr;
+    int4* meta_m = nullptr;
+    float* lat = nullptr;
+    if (want_grad) {
+        flags_m = (int32_t*)take(p.flags_bytes);
+        st_m = (int2*)take(p.st_bytes);
+        meta_m = (int4*)take(p.meta_bytes);
+        bigs_m = (int32_t*)take(p.big_bytes);
+        unsigned long long* keys = (unsigned long long*)take(q.keys_bytes);
+        int32_t* m_src = (int32_t*)take(q.arcs_bytes);
+        int32_t* m_cls = (int32_t*)take(q.arcs_bytes);
+        int32_t* m_dst = (int32_t*)take(q.arcs_bytes);
+        perm = (int32_t*)take(q.arcs_bytes);
+        cpos = (int32_t*)take(q.arcs_bytes);
+        cbeg = (int32_t*)take(q.cbeg_bytes);
+        lat = (float*)take(q.lattice_bytes);
+        grammar_mirror_kernel<<<g, max_arcs > 1024 ? NT_BIG : NT_SMALL, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v,
+                                                                               max_states, max_arcs, q.p2, keys, m_src, m_cls, m_dst, perm,
+                                                                               cpos, cbeg);
+        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(mirror)");
+        grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, m_src, m_cls, m_dst, v, max_states, max_arcs,
+                                              max_arcs > 0 ? max_arcs : 1, flags_m, st_m, meta_m, bigs_m);
+        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(mirrored plan)");
+    }
+    ctc_grammar_grad_kernel<<<b, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, which, flags, st, meta, bigs, flags_m,
+                                                        st_m, meta_m, bigs_m, perm, cpos, cbeg, p.stage, t, b, v, g, max_states, max_arcs,
+                                                        out_logp, lat, dlogits);
+    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(sweep)");
+    if (want_grad) {
+        grammar_grad_rows_kernel<<<vocr_cdiv((long)t * b, 4), 256, 0, s>>>(logits, clp, lens, canon, weights, out_logp, t, b, v, dlogits);
+        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(rows)");
     }
     return VOCR_OK;
 }

@@ -4,10 +4,12 @@ the network's output itself.
 
 WHAT THE NUMBER IS: for a line and a grammar (a deterministic finite automaton over the alphabet's symbol classes), the probability
 under the CTC model that the line's collapsed labelling is accepted: the exact sum over ALL frame paths, no beam, no hypothesis, no
-pruning.  WHAT IT IS NOT: there are no weights on the arcs (no language model, no n-gram), there is no gradient, and the "best" result is
+pruning.  WHAT IT IS NOT: there are no weights on the arcs (no language model, no n-gram), and the "best" result is
 the best single PATH through the grammar (frame path and state sequence), not the most probable accepted LABELLING (which would sum the
 paths of each labelling first).  Characters are compared as the alphabet's symbol strings: indices with the same string are one class
-and share an arc.  An automaton of more than 8192 states + arcs does not fit the kernel; larger lexicons stay with WordBeamDecoder."""
+and share an arc.  An automaton of more than 8192 states + arcs does not fit the kernel; larger lexicons stay with WordBeamDecoder.
+The gradient of a line's ln P under ITS OWN grammar (vocr_ctc_grammar_grad) is GrammarMatcher.line_log_prob; the training criterion
+built on it is grammar_loss.GrammarCTCLoss."""
 from collections import namedtuple
 
 import numpy as np
@@ -249,8 +251,9 @@ class _Nfa(object):
         return a, b
 
 
-def _determinize(nfa, start, end):
-    """Subset construction.  (per state a dict class -> state, accept flags); state 0 is the start."""
+def _determinize(nfa, start, end, max_cells=None, what=None):
+    """Subset construction.  (per state a dict class -> state, accept flags); state 0 is the start.  max_cells: a ValueError under
+    the name `what` once the states + arcs made so far exceed it (before minimisation)."""
     closures = {}
 
     def closure(states):
@@ -269,8 +272,11 @@ def _determinize(nfa, start, end):
 
     first = closure([start])
     index, order, trans = {first: 0}, [first], []
-    k = 0
+    k = arcs = 0
     while k < len(order):
+        if max_cells is not None and len(order) + arcs > max_cells:
+            raise ValueError("%s: the subset construction has passed %d states + %d arcs, more than %d: too large to build (the kernel "
+                             "takes %d cells)" % (what, len(order), arcs, max_cells, ops.GRAMMAR_CELLS_MAX))
         moves = {}
         for n in order[k]:
             for cset, tgt in nfa.arcs[n]:
@@ -284,6 +290,7 @@ def _determinize(nfa, start, end):
                 order.append(nxt)
             row[c] = index[nxt]
         trans.append(row)
+        arcs += len(row)
         k += 1
     return trans, [end in s for s in order]
 
@@ -344,9 +351,21 @@ def _minimize(trans, accept):
     return out_t, out_a
 
 
+class _Marker(object):
+    def __init__(self, name):
+        self.name = name
+
+    def __repr__(self):
+        return "Grammar." + self.name
+
+
 class Grammar(object):
     """A minimised deterministic automaton over the alphabet's symbol classes: dead and unreachable states removed, state 0 the start,
-    the arcs in the kernel's order (dst, class, src).  Build one with from_regex, from_words, contains or from_dfa."""
+    the arcs in the kernel's order (dst, class, src).  Build one with from_regex, from_words, contains, from_dfa, from_template or
+    from_labels."""
+
+    ANY = _Marker("ANY")                                    # from_template: exactly one arbitrary symbol
+    GAP = _Marker("GAP")                                    # from_template: any string, the empty one included
 
     def __init__(self, alphabet, trans, accept, name="grammar"):
         self.alphabet, self.name = alphabet, name
@@ -433,6 +452,51 @@ class Grammar(object):
         return cls(alphabet, trans, accept, name="contains %r%s" % (keyword, " (whole word)" if whole_word else ""))
 
     @classmethod
+    def from_labels(cls, alphabet, labels):
+        """Accepts exactly one labelling (a utf-8 string or a sequence of alphabet indices): the linear chain, whose score is the CTC
+        score of the labelling."""
+        lab = _labels(alphabet, alphabet.canonical_indices(), labels, "from_labels")
+        trans = [{c: k + 1} for k, c in enumerate(lab)] + [{}]
+        return cls(alphabet, trans, [False] * len(lab) + [True], name="a chain of %d labels" % len(lab))
+
+    @classmethod
+    def from_template(cls, alphabet, items, exclude=()):
+        """A transcript with holes.  `items` is a sequence of: a symbol (an alphabet index or one utf-8 character); a set, frozenset,
+        list or tuple of symbols (alternatives at one position); Grammar.ANY (exactly one arbitrary symbol); Grammar.GAP (any string,
+        the empty one included).  `exclude`: symbols that ANY and GAP do not stand for (a reserved placeholder).  Thompson NFA, subset
+        construction, minimisation, so the result is the minimal DFA and no labelling is counted twice.  A template whose DFA has
+        more than the kernel's 8192 states + arcs is a ValueError that names its sizes."""
+        canon, every = _classes(alphabet)
+
+        def sym(v):
+            return _labels(alphabet, canon, v if isinstance(v, str) else [v], "from_template")[0]
+
+        every = frozenset(every) - frozenset(sym(v) for v in exclude)
+        parts = []
+        for it in items:
+            if it is cls.ANY:
+                parts.append(("set", every))
+            elif it is cls.GAP:
+                parts.append(("rep", ("set", every), 0, None))
+            elif isinstance(it, (set, frozenset, list, tuple)):
+                if not len(it):
+                    raise ValueError("from_template: an empty set of alternatives")
+                parts.append(("set", frozenset(sym(v) for v in it)))
+            elif isinstance(it, str) and len(it) != 1:
+                raise ValueError("from_template: %r is not one character (a set or list gives alternatives)" % (it,))
+            else:
+                parts.append(("set", frozenset([sym(it)])))
+        nfa = _Nfa()
+        start, end = nfa.build(("cat", parts))
+        # a set of NFA states never holds more than the template's positions, but ANY behind a GAP can double the DFA per item
+        trans, accept = _determinize(nfa, start, end, max_cells=ops.GRAMMAR_CELLS_MAX * 64, what="from_template")
+        g = cls(alphabet, trans, accept, name="a template of %d items" % len(parts))
+        if g.n_states + g.n_arcs > ops.GRAMMAR_CELLS_MAX:
+            raise ValueError("from_template: the template's minimal DFA has %d states + %d arcs, more than the kernel's %d cells"
+                             % (g.n_states, g.n_arcs, ops.GRAMMAR_CELLS_MAX))
+        return g
+
+    @classmethod
     def from_dfa(cls, alphabet, transitions, accept):
         """Explicit tables: `transitions[s]` a dict symbol -> state (a symbol is an alphabet index or one utf-8 character), `accept[s]`
         flags, state 0 the start.  Two symbols of one class must lead to the same state."""
@@ -492,6 +556,47 @@ def group_grammars(grammars, T, B, want_best):
     return groups
 
 
+def lattice_chunks(T, B, max_states, max_arcs, max_lattice_bytes=None):
+    """The batch cut into the fewest consecutive ranges [b0, b1) of lines whose stored forward rows, T * lines * (max_states + max_arcs)
+    * 4 bytes, stay within max_lattice_bytes (None: the kernel's 2 GiB) in one vocr_ctc_grammar_grad call each."""
+    limit = ops.GRAMMAR_LATTICE_MAX_BYTES if max_lattice_bytes is None else min(int(max_lattice_bytes), ops.GRAMMAR_LATTICE_MAX_BYTES)
+    one = ops.grammar_lattice_bytes(T, 1, max_states, max_arcs)
+    per = limit // one
+    if per < 1:
+        raise ValueError("GrammarMatcher: one line's forward rows, %d frames x (%d states + %d arcs) x 4 = %d bytes, exceed the limit of "
+                         "%d bytes" % (T, max_states, max_arcs, one, limit))
+    return [(b0, min(b0 + per, B)) for b0 in range(0, B, per)]
+
+
+def grammar_grad_chunked(logits, lens_dev, packed, which_dev, canon, weight, max_lattice_bytes=None):
+    """(logp [B], dlogits [T,B,V]) of ops.ctc_grammar_grad with the constant weight `weight` per line, in as many calls as the stored
+    rows need.  Every call gets the same packed tables, so a line's bits do not depend on where the batch is cut."""
+    T, B = int(logits.shape[0]), int(logits.shape[1])
+    chunks = lattice_chunks(T, B, packed["max_states"], packed["max_arcs"], max_lattice_bytes)
+    w = torch.full((B,), float(weight), dtype=torch.float32, device=logits.device)
+    if len(chunks) == 1:
+        return ops.ctc_grammar_grad(logits, lens_dev, packed, which_dev, canon, w)
+    outs = [ops.ctc_grammar_grad(logits[:, b0:b1], lens_dev[b0:b1], packed, which_dev[b0:b1], canon, w[b0:b1]) for b0, b1 in chunks]
+    return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs], dim=1)
+
+
+class _LineLogProbFn(torch.autograd.Function):
+    """ln P [B]; the gradient with respect to the logits is saved by the forward call and scaled per line in the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, lens_dev, packed, which_dev, canon, max_lattice_bytes):
+        logp, dlogits = grammar_grad_chunked(logits, lens_dev, packed, which_dev, canon, 1.0, max_lattice_bytes)
+        ctx.save_for_backward(dlogits)
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        (dlogits,) = ctx.saved_tensors
+        # a line with ln P = -inf has zero rows; its incoming gradient may be anything, inf included, and must not make them NaN
+        scale = torch.nan_to_num(ops._f32c(dlogp), nan=0.0, posinf=0.0, neginf=0.0).reshape(1, -1, 1)
+        return (dlogits * scale,) + (None,) * 5
+
+
 class GrammarMatcher(object):
     """Scores the model's output frames against grammars."""
 
@@ -515,6 +620,35 @@ class GrammarMatcher(object):
         if len(outs) == 1:
             return outs[0]
         return tuple(torch.cat([o[k] for o in outs], dim=1) if want_best or k == 0 else None for k in range(4))
+
+    def line_log_prob(self, model_output, lens, grammars, which, max_lattice_bytes=None):
+        """ln P [B] (fp32 device tensor) that line b's text is in grammars[which[b]], with autograd to `model_output` ([T,B,V] logits on
+        the device).  `grammars` a list of Grammar, `which` B indices into it (several lines may share a grammar).  The kernel stores
+        T * lines * (largest states + largest arcs) * 4 bytes of forward rows per call; a batch that needs more than max_lattice_bytes
+        (default, and at most, the kernel's 2 GiB) is cut into consecutive chunks of lines, with bit-identical results.  Without
+        autograd (torch.no_grad, or an output that needs no gradient) only the forward sweep runs."""
+        grammars = list(grammars)
+        dev = model_output.device
+        B = int(model_output.shape[1])
+        which = [int(k) for k in (which.tolist() if torch.is_tensor(which) else which)]
+        if len(which) != B:
+            raise ValueError("GrammarMatcher.line_log_prob: %d entries of which for %d lines" % (len(which), B))
+        if not grammars or min(which) < 0 or max(which) >= len(grammars):
+            raise ValueError("GrammarMatcher.line_log_prob: which must index the %d grammars" % len(grammars))
+        for g in grammars:
+            if g.n_states + g.n_arcs > ops.GRAMMAR_CELLS_MAX:
+                raise ValueError("GrammarMatcher: %s has %d states + %d arcs, more than the kernel's %d cells"
+                                 % (g.name, g.n_states, g.n_arcs, ops.GRAMMAR_CELLS_MAX))
+        packed = pack_grammars(grammars, dev)
+        if packed["max_states"] + packed["max_arcs"] > ops.GRAMMAR_CELLS_MAX:
+            raise ValueError("GrammarMatcher.line_log_prob: the largest state count %d plus the largest arc count %d of the grammars exceed "
+                             "the kernel's %d cells: score them in separate calls" % (packed["max_states"], packed["max_arcs"],
+                                                                                     ops.GRAMMAR_CELLS_MAX))
+        which_dev = torch.as_tensor(which, dtype=torch.int32).to(dev)
+        lens_dev = ops._lens_canon("GrammarMatcher.line_log_prob", model_output, lens, None)
+        if not (torch.is_grad_enabled() and model_output.requires_grad):
+            return ops.ctc_grammar_grad(model_output.detach(), lens_dev, packed, which_dev, self.canon(dev))[0]
+        return _LineLogProbFn.apply(model_output, lens_dev, packed, which_dev, self.canon(dev), max_lattice_bytes)
 
     def match(self, model_output, lens, grammars):
         """`model_output` [T,B,V] logits on the device, `lens` the lines' frame counts, `grammars` a list of Grammar.  Returns

@@ -1568,7 +1568,7 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
     [states], and the ints "max_states", "max_arcs" (bounds of one automaton's sizes); `canon` int32 [V] device tensor of the symbol
     classes or None.  Returns, on the device, (logp fp32 [B,G]; best fp32 [B,G]; labels int32 [B,G,T]; label_lens int32 [B,G]), the last
     three None without want_best (no max pass runs and no back pointers are allocated; logp has the same bits either way).  -inf / -inf /
-    length -1 where nothing is accepted and, for every line, for an automaton that breaks a rule.  No weights on arcs, no gradient; best
+    length -1 where nothing is accepted and, for every line, for an automaton that breaks a rule.  No weights on arcs (the gradient: ctc_grammar_grad); best
     is the best PATH, not the most probable accepted labelling.  Shapes, dtypes and the kernel's limits are checked here; the CONTENTS of
     the tables stay on the device and are not read back (that would cost a synchronise per call): the kernel validates every automaton
     against "max_states" / "max_arcs" and its own rules, but state_off[-1] <= accept.numel() and arc_off[-1] <= src.numel() are trusted,
@@ -1606,6 +1606,63 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
          _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(logp), _p(best), _p(labels), _p(out_lens), T, _p(ws), ws.numel() * 4,
          _stream())
     return logp, best, labels, out_lens
+
+
+GRAMMAR_LATTICE_MAX_BYTES = 1 << 31
+
+
+def grammar_lattice_bytes(T, B, max_states, max_arcs):
+    """What vocr_ctc_grammar_grad stores of B lines' forward rows."""
+    return T * B * (max_states + max_arcs) * 4
+
+
+def ctc_grammar_grad(logits, lens, grammars_packed, which, canon=None, weights=None):
+    """Grammar-constrained CTC scores and gradient (vocr_ctc_grammar_grad) on raw logits [T,B,V].  `lens`, `grammars_packed`, `canon` as
+    for ctc_grammar_scores; `which` int32 device tensor [B]: line b is scored against automaton which[b] alone (several lines may share
+    one); `weights` None or an fp32 device tensor [B].  Returns, on the device, (logp fp32 [B] = ln P(line b's labelling is accepted by
+    its automaton), the bits of ctc_grammar_scores' logp[b, which[b]] for the same packed tables; dlogits), dlogits None without weights,
+    else fp32 [T,B,V] = the gradient with respect to the raw logits of sum_b weights[b] * logp[b] over the lines with a finite score
+    (rows past `lens`, and the rows of a line whose score is -inf, whose automaton breaks a rule or whose which[b] is outside [0, G),
+    are zeros).  Without weights only the forward sweep runs and nothing is stored; with them the forward rows are, T * B * (max_states
+    + max_arcs) * 4 bytes, at most 2 GiB per call: GrammarMatcher.line_log_prob cuts a batch that needs more."""
+    gp = grammars_packed
+    names = ("state_off", "arc_off", "src", "cls", "dst", "accept")
+    _need_gpu(logits, which, *[gp[k] for k in names])
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    dev = logits.device
+    for k in names:
+        if gp[k].dtype != torch.int32 or gp[k].dim() != 1:
+            raise RuntimeError("ctc_grammar_grad: grammars_packed[%r] must be a 1-d int32 tensor" % k)
+    G = int(gp["state_off"].numel()) - 1
+    if G < 1 or gp["arc_off"].numel() != G + 1 or not (gp["src"].numel() == gp["cls"].numel() == gp["dst"].numel()):
+        raise RuntimeError("ctc_grammar_grad: need state_off and arc_off of G + 1 >= 2 entries and src, cls, dst of one length "
+                           "(state_off %d, arc_off %d, src %d, cls %d, dst %d)" % (gp["state_off"].numel(), gp["arc_off"].numel(),
+                                                                                  gp["src"].numel(), gp["cls"].numel(), gp["dst"].numel()))
+    if which.dtype != torch.int32 or tuple(which.shape) != (B,):
+        raise RuntimeError("ctc_grammar_grad: which must be int32 [B] (which %s %s, B=%d)" % (tuple(which.shape), which.dtype, B))
+    ms, ma = int(gp["max_states"]), int(gp["max_arcs"])
+    nbytes = _lib.load().vocr_ctc_grammar_grad_workspace_bytes(T, B, V, G, ms, ma, 0 if weights is None else 1)
+    if nbytes == 0:
+        raise RuntimeError("ctc_grammar_grad: unsupported shape (T=%d B=%d V=%d G=%d max_states=%d max_arcs=%d; 2 <= V <= 256, "
+                           "max_states >= 1, max_states + max_arcs <= %d, T * B * G < 2^31, with weights T * B * (max_states + "
+                           "max_arcs) * 4 bytes of stored rows <= 2 GiB)" % (T, B, V, G, ms, ma, GRAMMAR_CELLS_MAX))
+    lens_dev = _lens_canon("ctc_grammar_grad", logits, lens, canon)
+    dlogits = None
+    if weights is not None:
+        _need_gpu(weights)
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (B,):
+            raise RuntimeError("ctc_grammar_grad: weights must be fp32 [B] (weights %s %s, B=%d)" % (tuple(weights.shape), weights.dtype, B))
+        weights = weights.detach().contiguous()
+        dlogits = torch.empty_like(logits)
+    t = {k: gp[k].contiguous() for k in names}
+    which = which.contiguous()
+    logp = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    call("vocr_ctc_grammar_grad", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G, _p(t["src"]),
+         _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(which), _p(weights), _p(logp), _p(dlogits), _p(ws), ws.numel() * 4,
+         _stream())
+    return logp, dlogits
 
 
 AUGMENT_REC_WORDS = 24
