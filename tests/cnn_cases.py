@@ -2,10 +2,10 @@
 tests/test_cnn_ref_cpu.py holds them to being fair to an honest fp32 convolution and to rejecting the seam mutants of tests/cnn_ref.py).
 Importing this module needs no GPU and no library.
 
-Buffers follow tests/gemm_ref.py (same GUARD and SENTINEL): a tensor the kernel READS sits between guard bands of NaN, so a read outside
-it reaches the result; a tensor the kernel WRITES (outputs, and workspaces of exactly the bytes their *_workspace_bytes query answers)
-starts as NaN between bands of the sentinel bit pattern, so an element the kernel leaves out, or a workspace word it reads without having
-written it, shows as NaN and a store outside shows as a touched band.
+Buffers are the guarded ones of tests/guarded.py (re-exported here): a tensor the kernel READS sits between guard bands of NaN, so a read
+outside it reaches the result; a tensor the kernel WRITES (outputs, and workspaces of exactly the bytes their *_workspace_bytes query
+answers) starts as NaN between bands of the sentinel bit pattern, so an element the kernel leaves out, or a workspace word it reads without
+having written it, shows as NaN and a store outside shows as a touched band.
 
 Tables: every row is a LAUNCH shape (n, cin, h, w, cout) - cin the contraction channels, cout the channels of the tensor written; a data
 gradient of a layer (a -> b) is the launch (n, b, h, w, a) with the layer's data-gradient pack.  A table is not a cross product:
@@ -19,54 +19,7 @@ The values of each axis sit on the seams of the kernels (conv_wino.hip, conv.hip
   fp16                      tiles of 8 / 12 / 16 rows x 32 / 64 pixels, Cin in chunks of 16, Cout around 64 / 128, rows padded to ceil8(W) + 8"""
 import torch
 
-from tests.gemm_ref import GUARD, SENTINEL
-
-_NAN_WORD = {torch.float32: 0x7FC00000, torch.float16: 0x7E007E00}          # one 32-bit word of NaN in the tensor's own format
-
-
-# ---------------------------------------------------------------------------------------------------------------- guarded buffers
-class Guarded(object):
-    """A contiguous tensor of `shape` behind GUARD 32-bit words and in front of GUARD more, in one device allocation (the tensor starts
-    256 bytes into it: every alignment a kernel asks for holds).
-    data given: an operand - the bands hold NaN of the tensor's format.  data None: an output or a workspace - the tensor starts as NaN and
-    the bands hold SENTINEL."""
-
-    def __init__(self, shape, dev, data=None, dtype=torch.float32, name=""):
-        shape = tuple(int(s) for s in shape)
-        numel = 1
-        for s in shape:
-            numel *= s
-        item = torch.empty(0, dtype=dtype).element_size()
-        assert numel > 0 and numel * item % 4 == 0, (shape, dtype)
-        self.words, self.name = numel * item // 4, name
-        self.band = SENTINEL if data is None else _NAN_WORD[dtype]
-        self.buf = torch.full((GUARD + self.words + GUARD,), self.band, dtype=torch.int32, device=dev)
-        body = self.buf[GUARD:GUARD + self.words].view(dtype)
-        self.t = body.view(shape)
-        if data is None:
-            self.t.fill_(float("nan"))
-        else:
-            assert tuple(data.shape) == shape, (tuple(data.shape), shape)
-            self.t.copy_(data.to(dev))
-        self.ptr = self.t.data_ptr()
-        assert self.ptr % 16 == 0
-
-    def outside_untouched(self):
-        """both bands still hold their fill, bit for bit"""
-        front, back = self.buf[:GUARD], self.buf[GUARD + self.words:]
-        return bool((front == self.band).all()) and bool((back == self.band).all())
-
-    def has_nan(self):
-        return bool(torch.isnan(self.t).any())
-
-    def bits(self):
-        return self.buf[GUARD:GUARD + self.words]
-
-
-def workspace(nbytes, dev, name="workspace"):
-    """a workspace of exactly `nbytes` (what the library's size query answered), NaN-filled, a sentinel band behind it; None for 0 bytes"""
-    assert nbytes % 4 == 0
-    return Guarded((nbytes // 4,), dev, name=name) if nbytes else None
+from tests.guarded import Guarded, workspace          # noqa: F401  (the guarded buffers live in tests/guarded.py; the conv, x6 and augment suites take them from here)
 
 
 # ---------------------------------------------------------------------------------------------------------------- tables
