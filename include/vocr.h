@@ -684,6 +684,35 @@ int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b
                           const int32_t* which, const float* weights, float* out_logp, float* dlogits,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- grammar-constrained CTC prefix beam search: the most probable labellings a deterministic automaton accepts ---- */
+/* vocr_ctc_beam_search - the same inputs, classes, optional character n-gram tables, score formula, total order, pruning, limits
+ * (1 <= nbest <= beam <= 128, v <= 256, t * b * beam < 2^31), outputs and workspace (the node pool) - restricted to the labellings
+ * that line b's automaton which[b] accepts.  The g automata are concatenated as DENSE tables: automaton k has the states
+ * g_state_off[k] .. g_state_off[k+1] (g_state_off[g] = all states) of dfa_next[states][v] (the LOCAL state after class c, -1: no arc;
+ * local state 0 is the start; only canonical columns are read) and dfa_dist[states] (the fewest symbols from the state to an
+ * accepting one: 0 exactly for accepting states, so there is no accept array).  All device int32; which[B] device int32.  The
+ * automaton is deterministic, so a prefix has one state, each beam carries it, and the exact prefix merge is unchanged.  With
+ * rem = lens[b] - 1 - t frames left after frame t, an extension by class c of a beam in state s is a candidate only if
+ * n = dfa_next[s][c] is a state of the automaton and 0 <= dfa_dist[n] <= rem, and a stay only if 0 <= dfa_dist[s] <= rem: every
+ * further symbol needs a frame, so only prefixes without an accepted completion are dropped (a lower bound: the blank between
+ * repeated symbols is not counted).  The final ranking keeps accepting states only.  The beam may run empty (the language needs more
+ * symbols than the line has frames): ranks the search did not fill have length 0 and total -inf, as in vocr_ctc_beam_search.
+ * lens[b] = 0: the empty labelling iff state 0 accepts.  Device contents are never trusted: which[b] outside [0, g) or a state range
+ * that is empty, reversed or past g_state_off[g] gives that line no hypothesis, a next state outside the automaton counts as no arc, a
+ * negative distance as "cannot accept"; none of them becomes a load address.  Under the one-state automaton that accepts everything
+ * the search takes the decisions of vocr_ctc_beam_search.  WHAT IT IS NOT: exact beyond the beam (a labelling whose prefix fell out
+ * of the beam is lost, as in every beam search), weighted (no weights on the arcs; the LM is the character n-gram), or
+ * non-deterministic.  There is no limit on the automaton's size but the memory of the dense tables (states * v * 4 bytes).  Only
+ * integer LDS atomics; results are bit-identical from run to run.  Bad arguments (g < 1, a NULL table, a short workspace) fail with
+ * VOCR_EINVAL before any launch.  Workspace from vocr_ctc_grammar_beam_workspace_bytes (0 for an unsupported shape). */
+size_t vocr_ctc_grammar_beam_workspace_bytes(int t, int b, int v, int beam, int nbest);
+int vocr_ctc_grammar_beam_search(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam, int nbest,
+                                 const int32_t* g_state_off, const int32_t* dfa_next, const int32_t* dfa_dist, int g,
+                                 const int32_t* which, const float* lm_logp, const int32_t* lm_next, const float* lm_eos,
+                                 int lm_states, int lm_start, float lm_weight, float insertion_bonus, float prune_logp,
+                                 int32_t* out_labels, int32_t* out_lens, float* out_scores,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- edit statistics: compute_cer_wer of test_on_val (src/textutils.py:264-351, src/train_cnn_lstm.py:32-100) and src/edit_dist_trace.py ---- */
 /* Levenshtein statistics (unit costs) of np (hypothesis, reference) pairs that are already on the device: distances and lengths over
  * characters and over the tokens of form_tokenized_words, and - on request - the operation trace.  Integer arithmetic: every output

@@ -18,7 +18,7 @@ from .ctc import CTCLoss                                                        
 from .risk import MinErrorRateLoss                                                      # noqa: F401,E402
 from .entropy import EntropyRegularizedCTCLoss                                          # noqa: F401,E402
 from .grammar_loss import GrammarCTCLoss                                                # noqa: F401,E402
-from .decoder import ArgmaxDecoder, BeamDecoder, WordBeamDecoder                        # noqa: F401,E402
+from .decoder import ArgmaxDecoder, BeamDecoder, GrammarBeamDecoder, WordBeamDecoder    # noqa: F401,E402
 from .lm import CharNgramLM, WordNgramLM                                                # noqa: F401,E402
 from .model import CnnOcrModel                                                          # noqa: F401,E402
 from .train import FlatClampAdam, make_optimizer, seed_rank, train, train_async                                    # noqa: F401,E402
@@ -26,5 +26,5 @@ from .dataset import OcrDataset                                                 
 from .augment import AugmentParams, DeviceAugmenter                                     # noqa: F401,E402
 
 __all__ = ["DeviceAugmenter", "AugmentParams","Alphabet", "english_alphabet", "arabic_alphabet", "french_alphabet", "CTCLoss", "MinErrorRateLoss", "EntropyRegularizedCTCLoss", "GrammarCTCLoss", "ArgmaxDecoder", "BeamDecoder",
-           "WordBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "Grammar", "GrammarMatcher", "GrammarHits", "ErrorScorer", "ErrorStats", "OracleStats",
+           "WordBeamDecoder", "GrammarBeamDecoder", "CharNgramLM", "WordNgramLM", "CtcAligner", "KeywordSpotter", "KeywordHits", "Grammar", "GrammarMatcher", "GrammarHits", "ErrorScorer", "ErrorStats", "OracleStats",
            "CnnOcrModel", "FlatClampAdam", "make_optimizer", "seed_rank", "train", "train_async", "OcrDataset"]

@@ -6,6 +6,7 @@ import torch
 
 from . import ops
 from .align import alternatives_from_device, lines_from_arrays, one_copy
+from .grammar import Grammar, pack_dense_grammars
 from .textutils import uxxxx_to_utf8
 
 
@@ -156,6 +157,83 @@ class BeamDecoder:
         if lang is not None:
             raise ValueError("BeamDecoder: one alphabet per decoder (lang is not supported)")
         return _best_strings(*self._search(model_output, batch_actual_timesteps, 1), self.alphabet, uxxxx)
+
+
+class GrammarBeamDecoder:
+    """Grammar-constrained CTC prefix beam search on the GPU (vocr_ctc_grammar_beam_search): what the line READS, given that it is a
+    date, an amount or one of these part numbers.  BeamDecoder's search, LM, ranking and output formats, restricted to the labellings a
+    Grammar (vistaocr_amd.grammar) accepts: each beam carries its automaton state, and a prefix that the frames left cannot complete
+    leaves the beam at once.  `grammars`: one Grammar or a list; `which=` on the public methods takes one index into the list per line
+    (None: grammar 0 for every line).  A line whose language nothing in the beam reaches (or that needs more symbols than the line has
+    frames) has no hypothesis: "" / None / an empty n-best list, as with the other decoders.  It is a beam search: not exact beyond
+    the beam; the automata are deterministic and carry no weights (the LM is the character n-gram).  The sweep kernels' 8192 cells do
+    not apply: the dense tables are bounded by `max_table_bytes` alone."""
+
+    def __init__(self, alphabet, grammars, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None,
+                 max_table_bytes=1 << 30):
+        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
+            raise ValueError("GrammarBeamDecoder: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (beam, nbest))
+        if lm is not None and lm.logp.shape[1] != len(alphabet):
+            raise ValueError("GrammarBeamDecoder: the LM was resolved for %d symbols, the alphabet has %d"
+                             % (lm.logp.shape[1], len(alphabet)))
+        self.grammars = [grammars] if isinstance(grammars, Grammar) else list(grammars)
+        if not self.grammars:
+            raise ValueError("GrammarBeamDecoder: no grammar")
+        for g in self.grammars:
+            if len(g.alphabet) != len(alphabet):
+                raise ValueError("GrammarBeamDecoder: %s is over an alphabet of %d symbols, the decoder's has %d"
+                                 % (g.name, len(g.alphabet), len(alphabet)))
+        self.alphabet = alphabet
+        self.beam, self.nbest = int(beam), int(nbest)
+        self.lm, self.lm_weight, self.insertion_bonus, self.prune_logp = lm, float(lm_weight), float(insertion_bonus), prune_logp
+        self.max_table_bytes = int(max_table_bytes)
+        self._canon, self._packed = {}, {}
+
+    def _search_device(self, model_output, batch_actual_timesteps, nbest, which=None):
+        dev = model_output.device
+        key = str(dev)
+        if key not in self._canon:
+            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+            self._packed[key] = pack_dense_grammars(self.grammars, dev, self.max_table_bytes)
+        if which is not None:
+            which = [int(k) for k in (which.tolist() if torch.is_tensor(which) else which)]
+            if len(which) != int(model_output.shape[1]):
+                raise ValueError("GrammarBeamDecoder: %d entries of which for %d lines" % (len(which), int(model_output.shape[1])))
+            if min(which) < 0 or max(which) >= len(self.grammars):
+                raise ValueError("GrammarBeamDecoder: which must index the %d grammars" % len(self.grammars))
+        return ops.ctc_grammar_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._packed[key], which,
+                                           self._canon[key], self.beam, nbest, self.lm.to(dev) if self.lm is not None else None,
+                                           self.lm_weight, self.insertion_bonus, self.prune_logp)
+
+    def _search(self, model_output, batch_actual_timesteps, nbest, which=None):
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest, which)
+        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
+
+    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1, which=None):
+        """BeamDecoder.decode_aligned for the grammar search: (hypotheses, alignments)."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest), which)
+        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
+
+    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False, which=None):
+        """BeamDecoder.decode_alternatives for the grammar search: (hypotheses, per line a LineAlternatives of the best hypothesis, None
+        where the search found none).  The posteriors are those of the CTC model alone: the grammar and the LM rank the search, not the
+        edits, so an alternative may leave the language."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1, which)
+        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
+
+    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None, which=None):
+        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first, every one accepted by the line's grammar; an
+        empty list where the search found none."""
+        nbest = self.nbest if nbest is None else int(nbest)
+        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest, which))
+
+    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None, which=None):
+        """The best accepted hypothesis of each line in decode_greedy's format ("" for a line without one)."""
+        if lang is not None:
+            raise ValueError("GrammarBeamDecoder: one alphabet per decoder (lang is not supported)")
+        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1, which), self.alphabet, uxxxx)
 
 
 def _line_lengths(batch_actual_timesteps):

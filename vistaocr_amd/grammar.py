@@ -6,8 +6,10 @@ WHAT THE NUMBER IS: for a line and a grammar (a deterministic finite automaton o
 under the CTC model that the line's collapsed labelling is accepted: the exact sum over ALL frame paths, no beam, no hypothesis, no
 pruning.  WHAT IT IS NOT: there are no weights on the arcs (no language model, no n-gram), and the "best" result is
 the best single PATH through the grammar (frame path and state sequence), not the most probable accepted LABELLING (which would sum the
-paths of each labelling first).  Characters are compared as the alphabet's symbol strings: indices with the same string are one class
-and share an arc.  An automaton of more than 8192 states + arcs does not fit the kernel; larger lexicons stay with WordBeamDecoder.
+paths of each labelling first: decoder.GrammarBeamDecoder searches for that, over the dense tables of Grammar.dense_tables /
+pack_dense_grammars).  Characters are compared as the alphabet's symbol strings: indices with the same string are one class
+and share an arc.  An automaton of more than 8192 states + arcs does not fit the sweep kernels; larger lexicons stay with
+WordBeamDecoder or go to GrammarBeamDecoder, whose tables have no such limit.
 The gradient of a line's ln P under ITS OWN grammar (vocr_ctc_grammar_grad) is GrammarMatcher.line_log_prob; the training criterion
 built on it is grammar_loss.GrammarCTCLoss."""
 from collections import namedtuple
@@ -401,6 +403,30 @@ class Grammar(object):
                 return False
         return bool(self.accept[s])
 
+    def dense_tables(self):
+        """(next int32 [S,V], dist int32 [S]), the tables of the grammar-constrained beam search (vocr_ctc_grammar_beam_search):
+        next[s, c] the state after class c (-1: no arc; non-canonical columns are -1), dist[s] the fewest symbols from s to an
+        accepting state (0 exactly for the accepting states; -1 where none can be reached: the start of the empty language)."""
+        S, V = self.n_states, len(self._canon)
+        nxt = np.full((S, V), -1, dtype=np.int32)
+        back = [[] for _ in range(S)]
+        for s, row in enumerate(self._trans):
+            for c, d in row.items():
+                nxt[s, c] = d
+                back[d].append(s)
+        dist = np.full(S, -1, dtype=np.int32)
+        frontier = [s for s in range(S) if self.accept[s]]
+        dist[frontier] = 0
+        while frontier:
+            following = []
+            for d in frontier:
+                for s in back[d]:
+                    if dist[s] < 0:
+                        dist[s] = dist[d] + 1
+                        following.append(s)
+            frontier = following
+        return nxt, dist
+
     @classmethod
     def from_regex(cls, alphabet, pattern):
         """A WHOLE-LINE match of `pattern`: literals (utf-8; a symbol outside the alphabet is a ValueError), `.` (any symbol), `[abc]`,
@@ -528,6 +554,30 @@ def pack_grammars(grammars, device):
     return {"state_off": torch.from_numpy(s_off).to(device), "arc_off": torch.from_numpy(a_off).to(device), "src": cat("arc_src"),
             "cls": cat("arc_cls"), "dst": cat("arc_dst"), "accept": cat("accept"),
             "max_states": max(g.n_states for g in grammars), "max_arcs": max(g.n_arcs for g in grammars)}
+
+
+def pack_dense_grammars(grammars, device, max_table_bytes=1 << 30):
+    """The concatenated dense tables ops.ctc_grammar_beam_search takes, on `device`: state_off int32 [G+1], next int32 [states, V],
+    dist int32 [states].  The sweep kernels' 8192 cells do not bound them; their memory does: tables above max_table_bytes are a
+    ValueError that names the sizes."""
+    grammars = list(grammars)
+    if not grammars:
+        raise ValueError("pack_dense_grammars: no grammar")
+    V = len(grammars[0]._canon)
+    if any(len(g._canon) != V for g in grammars):
+        raise ValueError("pack_dense_grammars: the grammars are over alphabets of different sizes (%s)"
+                         % sorted({len(g._canon) for g in grammars}))
+    states = sum(g.n_states for g in grammars)
+    nbytes = states * (V + 1) * 4
+    if nbytes > max_table_bytes:
+        raise ValueError("pack_dense_grammars: %d states x %d symbols of dense tables take %d bytes, more than max_table_bytes=%d"
+                         % (states, V, nbytes, max_table_bytes))
+    tabs = [g.dense_tables() for g in grammars]
+    s_off = np.cumsum([0] + [g.n_states for g in grammars]).astype(np.int32)
+    return {"state_off": torch.from_numpy(s_off).to(device),
+            "next": torch.from_numpy(np.ascontiguousarray(np.concatenate([t[0] for t in tabs], axis=0))).to(device),
+            "dist": torch.from_numpy(np.ascontiguousarray(np.concatenate([t[1] for t in tabs]))).to(device),
+            "num_grammars": len(grammars), "num_states": int(states)}
 
 
 def group_grammars(grammars, T, B, want_best):

@@ -1332,6 +1332,61 @@ def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weig
     return labels, out_lens, scores
 
 
+def ctc_grammar_beam_search(logits, lens, dense_packed, which=None, canon=None, beam=16, nbest=1, lm=None, lm_weight=0.0,
+                            insertion_bonus=0.0, prune_logp=None):
+    """Grammar-constrained CTC prefix beam search (vocr_ctc_grammar_beam_search) over raw logits [T,B,V]: ctc_beam_search restricted to
+    the labellings that line b's automaton accepts.  `dense_packed`: the device tables of grammar.pack_dense_grammars (state_off int32
+    [G+1], next int32 [states,V], dist int32 [states]); `which`: one automaton index per line (any int sequence or tensor; None:
+    automaton 0 for every line; an index outside [0, G) gives that line no hypothesis); `lens`, `canon`, `lm` and the weights as for
+    ctc_beam_search.  Returns (labels int32 [B,nbest,T], lengths int32 [B,nbest], scores fp32 [B,nbest,3] = total, acoustic, LM), on
+    the device; a rank the search did not fill has length 0 and total -inf."""
+    _need_gpu(logits)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    dev = logits.device
+    lib = _lib.load()
+    nbytes = lib.vocr_ctc_grammar_beam_workspace_bytes(T, B, V, int(beam), int(nbest))
+    if nbytes == 0:
+        raise RuntimeError("ctc_grammar_beam_search: unsupported shape or beam (T=%d B=%d V=%d beam=%d nbest=%d; V <= 256, 1 <= nbest "
+                           "<= beam <= 128, T * B * beam < 2^31)" % (T, B, V, beam, nbest))
+    lens_dev = _lens_canon("ctc_grammar_beam_search", logits, lens, canon)
+    s_off, nxt, dist = dense_packed["state_off"], dense_packed["next"], dense_packed["dist"]
+    _need_gpu(s_off, nxt, dist)
+    G, states = s_off.numel() - 1, dist.numel()
+    if (G < 1 or s_off.dtype != torch.int32 or nxt.dtype != torch.int32 or dist.dtype != torch.int32 or tuple(nxt.shape) != (states, V)
+            or dist.dim() != 1 or states < 1 or int(dense_packed.get("num_states", states)) != states
+            or not (s_off.is_contiguous() and nxt.is_contiguous() and dist.is_contiguous())):
+        raise RuntimeError("ctc_grammar_beam_search: the dense tables do not match V=%d (state_off %s %s, next %s %s, dist %s %s)"
+                           % (V, tuple(s_off.shape), s_off.dtype, tuple(nxt.shape), nxt.dtype, tuple(dist.shape), dist.dtype))
+    if which is None:
+        which_dev = torch.zeros(B, dtype=torch.int32, device=dev)
+    elif torch.is_tensor(which):
+        which_dev = which.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        which_dev = torch.as_tensor([int(k) for k in which], dtype=torch.int32).to(dev)
+    if which_dev.numel() != B:
+        raise RuntimeError("ctc_grammar_beam_search: %d entries of which for %d lines" % (which_dev.numel(), B))
+    labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
+    out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
+    ws = _ws(nbytes, dev)
+    if lm is not None:
+        lp, nx, eos = lm["lm_logp"], lm["lm_next"], lm["lm_eos"]
+        _need_gpu(lp, nx, eos)
+        S = lp.shape[0]
+        if lp.shape != (S, V) or nx.shape != (S, V) or eos.shape != (S,) or lp.dtype != torch.float32 or nx.dtype != torch.int32:
+            raise RuntimeError("ctc_grammar_beam_search: LM tables do not match V=%d (lm_logp %s, lm_next %s, lm_eos %s)"
+                               % (V, tuple(lp.shape), tuple(nx.shape), tuple(eos.shape)))
+        lm_args = (_p(lp), _p(nx), _p(eos), S, int(lm["start"]))
+    else:
+        lm_args = (None, None, None, 0, 0)
+    prune = float("-inf") if prune_logp is None else float(prune_logp)
+    call("vocr_ctc_grammar_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(s_off), _p(nxt), _p(dist),
+         G, _p(which_dev), *lm_args, float(lm_weight), float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores), _p(ws),
+         ws.numel() * 4, _stream())
+    return labels, out_lens, scores
+
+
 _WORD_LM_INT = ("kind", "tok", "trie_next", "trie_tok", "off", "succ_tok", "succ_next", "back")
 _WORD_LM_FLOAT = ("trie_la", "succ_logp", "bow")
 
@@ -1569,7 +1624,7 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
     classes or None.  Returns, on the device, (logp fp32 [B,G]; best fp32 [B,G]; labels int32 [B,G,T]; label_lens int32 [B,G]), the last
     three None without want_best (no max pass runs and no back pointers are allocated; logp has the same bits either way).  -inf / -inf /
     length -1 where nothing is accepted and, for every line, for an automaton that breaks a rule.  No weights on arcs (the gradient: ctc_grammar_grad); best
-    is the best PATH, not the most probable accepted labelling.  Shapes, dtypes and the kernel's limits are checked here; the CONTENTS of
+    is the best PATH, not the most probable accepted labelling (ctc_grammar_beam_search / GrammarBeamDecoder search for that).  Shapes, dtypes and the kernel's limits are checked here; the CONTENTS of
     the tables stay on the device and are not read back (that would cost a synchronise per call): the kernel validates every automaton
     against "max_states" / "max_arcs" and its own rules, but state_off[-1] <= accept.numel() and arc_off[-1] <= src.numel() are trusted,
     as the header says - an offset beyond its array reads out of bounds.  grammar.pack_grammars always packs them consistently."""
