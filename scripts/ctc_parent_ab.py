@@ -23,13 +23,23 @@ labelling (the sweep, the host preamble and the class rule the scorers of a know
   logits at p_char 0.35 (43 - 67 labels: the rows in LDS) and 0.10 (5 - 24 labels: one position per lane), packed to the longest;
   vocr_ctc_entropy on the 1-best of the same search, scores only and with the gradient.
 
-Bits, both: outputs and workspace are filled with a constant before the call, so bytes that no kernel writes compare equal trivially;
+search (the three prefix beam searches: vocr_ctc_beam_search and vocr_ctc_grammar_beam_search, one templated kernel of ctc_beam.hip,
+  and vocr_ctc_word_beam_search), recorded and replayed as above.
+  Bits: every character case of tests/beam_cases.py (dense, variants, ties, come-back, intermediate beams, the K = 128, V = 256
+  launch) and its word cases, through the _run of tests/test_beam_fp64_gpu.py and tests/test_word_beam_fp64_gpu.py; the dense and trie
+  cases of tests/grammar_beam_cases.py; every call that the Sigma*, bad-index and poisoned-row, K = 128 alphabet and distance-rule
+  tests of tests/test_grammar_beam_gpu.py make.  SHA-256 of every output and of the whole workspace (the node pool).
+  Time: T 294, B 32, V 96, the English classes, peaky logits at p_char 0.35, K = 16 and 64: the character search and the grammar search
+  under the one-state automaton and under a date regex, without an LM and with the synthetic 6-gram of scripts/beam_bench.py; the word
+  search with the LM of scripts/word_beam_bench.py.
+
+Bits, all: outputs and workspace are filled with a constant before the call, so bytes that no kernel writes compare equal trivially;
 every digest pair must be equal, and the script exits 1 otherwise.
-Time, both: the whole call with HIP events, both libraries warmed up on every shape, then windows of --window calls alternating between
+Time, all: the whole call with HIP events, both libraries warmed up on every shape, then windows of --window calls alternating between
 the libraries for --rounds rounds.  Per shape and library: the median of the round medians, and the parent's own max - min over its
 rounds, which is the only margin: the new median must not exceed the parent's median plus that spread.
 
-    python scripts/ctc_parent_ab.py [--what loss|labelling] [--window 200] [--rounds 5] [--out profiles/ctc_<what>_ab.txt]"""
+    python scripts/ctc_parent_ab.py [--what loss|labelling|search] [--window 200] [--rounds 5] [--out profiles/ctc_<what>_ab.txt]"""
 import argparse
 import ctypes
 import functools
@@ -61,7 +71,9 @@ ENTRIES = {
     "vocr_ctc_keyword_scores": ("vocr_ctc_keyword_workspace_bytes", (2, 3, 4, 9, 11), (12, 13, 14), 15),
     "vocr_ctc_beam_search": ("vocr_ctc_beam_workspace_bytes", (2, 3, 4, 6, 7), (16, 17, 18), 19),
     "vocr_ctc_word_beam_search": ("vocr_ctc_word_beam_workspace_bytes", (2, 3, 4, 6, 7), (29, 30, 31), 32),
+    "vocr_ctc_grammar_beam_search": ("vocr_ctc_grammar_beam_workspace_bytes", (2, 3, 4, 6, 7), (21, 22, 23), 24),
 }
+SEARCHES = ("vocr_ctc_beam_search", "vocr_ctc_grammar_beam_search", "vocr_ctc_word_beam_search")
 
 
 def open_lib(path):
@@ -301,13 +313,75 @@ def labelling_timed_cases():
         yield "p_char %.2f 1-best" % p_char, M, entropy_calls(xd, lens, lab[:, 0, :M].contiguous(), ln[:, 0].contiguous(), cd, coeff)
 
 
-def labelling_tables(libs, args, say):
+def search_bit_cases():
+    """(case name, [(entry label, Replay)]): the three beam searches on the tests' own inputs"""
+    from tests import beam_cases as bc
+    from tests import grammar_beam_cases as gc
+    from tests import test_beam_fp64_gpu as tb
+    from tests import test_grammar_beam_gpu as tg
+    from tests import test_word_beam_fp64_gpu as tw
+    label = {"vocr_ctc_beam_search": "beam", "vocr_ctc_grammar_beam_search": "grammar", "vocr_ctc_word_beam_search": "word beam"}
+    for name in bc.CHAR_DENSE + bc.CHAR_VARIANTS + bc.CHAR_TIES + bc.CHAR_COMEBACK + bc.CHAR_INTERMEDIATE + ["big_K128_V256"]:
+        case = bc.char_case(name)
+        yield "char " + name, [("beam", record(tb._run, case.x, case.lens, case.K, case.nbest, canon=case.canon, lm=case.lm,
+                                               alpha=case.alpha, beta=case.beta, prune=case.prune)[0])]
+    for name in bc.WORD_DENSE + ["w_big_K128_V256", "w_tie_lm_K6"]:
+        case = bc.word_case(name)
+        yield "word " + name, [("word beam", record(tw._run, case.x, case.lens, case.K, case.nbest, case.lm, canon=case.canon,
+                                                    alpha=case.alpha, beta=case.beta, oov=case.oov)[0])]
+    for name in gc.DENSE + gc.TRIE:
+        yield "grammar " + name, [("grammar", record(tg._search, gc.case(name))[0])]
+    fns = [(tg.test_sigma_star_is_the_existing_kernel, (K, with_lm)) for K in (1, 16, 128) for with_lm in (False, True)]
+    fns += [(f, ()) for f in (tg.test_per_line_automata_bad_indices_and_a_poisoned_row, tg.test_smallest_and_largest_alphabet_at_K128,
+                              tg.test_corners_of_the_distance_rule)]
+    for fn, a in fns:
+        calls = [c for c in record(fn, *a) if c.name in SEARCHES]
+        yield "%s%s" % (fn.__name__[5:35], a if a else ""), [("%s %d" % (label[c.name], i), c) for i, c in enumerate(calls)]
+
+
+def search_timed_cases():
+    """(shape name, K, [(entry label, Replay)]): T 294, B 32, V 96, the English classes, peaky logits at p_char 0.35, nbest 1; the
+    character search, the grammar search under the one-state automaton and under scripts/grammar_beam_bench.py's date regex, without an
+    LM and with scripts/beam_bench.py's synthetic 6-gram; the word search with scripts/word_beam_bench.py's LM, open vocabulary"""
+    import tempfile
+    import vistaocr_amd as va
+    from tests import beam_data as bd
+    from tests import word_beam_data as wd
+    from vistaocr_amd import ops
+    from vistaocr_amd.grammar import Grammar, pack_dense_grammars
+    T, B, V = 294, 32, 96
+    al = va.english_alphabet()
+    canon = np.array(al.canonical_indices())
+    cls = np.nonzero(canon == np.arange(V))[0][1:]
+    cd = torch.as_tensor(canon, dtype=torch.int32).cuda()
+    xd = torch.from_numpy(bd.peaky_logits(np.random.default_rng(7), T, B, V, classes=cls, p_char=0.35)).cuda()
+    lens = [T] * B
+    tmp = tempfile.mkdtemp()
+    path = bd.write_char_arpa(os.path.join(tmp, "char6.arpa"), [al.idx_to_char[c] for c in range(1, 40)], order=6, lines=600, seed=1)
+    clm = va.CharNgramLM.from_arpa(path, al).to("cuda")
+    rng = np.random.default_rng(5)
+    words, wts = wd.make_lexicon(rng, 20000, min_len=2, max_len=10)
+    sents = wd.make_sentences(rng, words, wts, 40000 + B)
+    wlm = va.WordNgramLM.from_arpa(wd.write_word_arpa(os.path.join(tmp, "word3.arpa"), words, wts, sents[:40000], seed=6), al).to("cuda")
+    sigma, date = (pack_dense_grammars([Grammar.from_regex(al, r)], "cuda") for r in (".*", r"\d{4}-\d\d-\d\d"))
+    for K in (16, 64):
+        for lname, lm, a, bb in (("no LM", None, 0.0, 0.0), ("6-gram", clm, 0.8, 1.0)):
+            def go():
+                ops.ctc_beam_search(xd, lens, cd, K, 1, lm, a, bb)
+                ops.ctc_grammar_beam_search(xd, lens, sigma, None, cd, K, 1, lm, a, bb)
+                ops.ctc_grammar_beam_search(xd, lens, date, None, cd, K, 1, lm, a, bb)
+            yield lname, K, list(zip(("beam", "g. Sigma*", "g. date"), record(go)))
+        yield "word 3-gram", K, [("word beam", record(ops.ctc_word_beam_search, xd, lens, cd, wlm, K, 1, 0.8, 0.5, -5.0)[0])]
+
+
+def replay_tables(libs, args, say, bit_cases, timed_cases, col="M"):
+    """the two tables of a mode made of recorded calls; `col`: what the timed cases' second field is"""
     new, parent = libs
     say("bits: SHA-256 (first 12 hex digits) of every output and of the whole workspace, all filled with %g before the call" % FILL)
     fmt = "%-42s %-11s | %-64s | %s"
     say(fmt % ("case", "entry", "outputs in the C order, workspace", "new vs parent"))
     differ = pairs = 0
-    for case, calls in labelling_bit_cases():
+    for case, calls in bit_cases():
         for label, call in calls:
             assert call.sizes(new) == call.sizes(parent) > 0, "the two libraries size the workspace differently: %s %s" % (case, label)
             dn, dp = call.digests(new), call.digests(parent)
@@ -316,12 +390,12 @@ def labelling_tables(libs, args, say):
             say(fmt % (case, label, " ".join(d[:12] for d in dn), "equal" if not bad else "DIFFER (parent %s)" % " ".join(d[:12] for d in dp)))
     say("digest pairs: %d, of which differ: %d" % (pairs, differ))
     say("")
-    say("time: the whole call (class log-probabilities and every kernel behind them), HIP events, us; per round the median of a window of "
+    say("time: the whole call (every kernel behind it), HIP events, us; per round the median of a window of "
         "%d calls, the libraries alternating, %d rounds after a warm-up window of each" % (args.window, args.rounds))
     tfmt = "%-17s %3s %-9s | %9s %9s %9s | %9s | %s"
-    say(tfmt % ("shape", "M", "entry", "parent", "p. spread", "new", "new - p.", "new <= parent + spread"))
+    say(tfmt % ("shape", col, "entry", "parent", "p. spread", "new", "new - p.", "new <= parent + spread"))
     slower = 0
-    for shape, M, calls in labelling_timed_cases():
+    for shape, M, calls in timed_cases():
         for label, call in calls:
             for lib in libs:
                 window(call, lib, args.window)
@@ -376,10 +450,11 @@ def main():
     ap.add_argument("--window", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--parent", default=os.path.join(ROOT, "scripts", "_cut", "libvocr.so"))
-    ap.add_argument("--what", choices=("loss", "labelling"), default="loss")
+    ap.add_argument("--what", choices=("loss", "labelling", "search"), default="loss")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out = args.out or os.path.join(ROOT, "profiles", "ctc_mirror_ab.txt" if args.what == "loss" else "ctc_labelling_ab.txt")
+    out = args.out or os.path.join(ROOT, "profiles", {"loss": "ctc_mirror_ab.txt", "labelling": "ctc_labelling_ab.txt",
+                                                      "search": "ctc_search_ab.txt"}[args.what])
     assert args.window >= 200 and args.rounds >= 5
     new, parent = open_lib(_lib.LIB_PATH), open_lib(args.parent)
     libs = (new, parent)
@@ -392,7 +467,12 @@ def main():
     say("device: %s" % torch.cuda.get_device_name(0))
     say("new: %s   parent: %s" % (os.path.relpath(_lib.LIB_PATH, ROOT), os.path.relpath(args.parent, ROOT)))
     say("")
-    differ, slower = (loss_tables if args.what == "loss" else labelling_tables)(libs, args, say)
+    if args.what == "loss":
+        differ, slower = loss_tables(libs, args, say)
+    elif args.what == "labelling":
+        differ, slower = replay_tables(libs, args, say, labelling_bit_cases, labelling_timed_cases)
+    else:
+        differ, slower = replay_tables(libs, args, say, search_bit_cases, search_timed_cases, col="K")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return 1 if differ or slower else 0

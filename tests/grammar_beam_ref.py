@@ -1,4 +1,4 @@
-"""CPU restatement of vocr_ctc_grammar_beam_search (vistaocr_amd/csrc/ctc_grammar_beam.hip) in fp64 numpy for one line.  Test helper
+"""CPU restatement of vocr_ctc_grammar_beam_search (vistaocr_amd/csrc/ctc_beam.hip, the GRAMMAR instantiation) in fp64 numpy for one line.  Test helper
 only: the product never imports it.
 
 It is tests/beam_ref.py's beam_search (whose helpers it imports) plus what the grammar adds: every beam carries the state of a

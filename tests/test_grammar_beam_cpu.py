@@ -130,6 +130,24 @@ def test_pack_dense_grammars_and_the_cell_limit():
         va.GrammarBeamDecoder(al, a, beam=4, nbest=5)
 
 
+def test_which_is_the_grammar_decoders_alone():
+    """The search decoders share their public methods, which hand `which=` to the decoder's own search as it came: a decoder whose
+    search takes no such argument refuses it with a TypeError, and `lang=` is refused under the decoder's own name - both before any
+    device is touched."""
+    import torch
+    al = va.english_alphabet()
+    x = torch.zeros(4, 1, len(al))
+    for method in ("decode", "decode_nbest", "decode_aligned", "decode_alternatives"):
+        with pytest.raises(TypeError, match="which"):
+            getattr(va.BeamDecoder(al), method)(x, [4], which=[0])
+    with pytest.raises(ValueError, match=r"^BeamDecoder: one alphabet per decoder \(lang is not supported\)$"):
+        va.BeamDecoder(al).decode(x, [4], lang="en")
+    with pytest.raises(ValueError, match=r"^GrammarBeamDecoder: one alphabet per decoder \(lang is not supported\)$"):
+        va.GrammarBeamDecoder(al, Grammar.from_regex(al, r"\d")).decode(x, [4], lang="en", which=[0])
+    with pytest.raises(ValueError, match=r"^BeamDecoder: need 1 <= nbest <= beam <= 128 \(beam=129 nbest=1\)$"):
+        va.BeamDecoder(al, beam=129)
+
+
 def test_host_checks_without_a_device():
     from vistaocr_amd import _lib
     lib = _lib.load()

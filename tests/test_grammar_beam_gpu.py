@@ -1,4 +1,4 @@
-"""GPU: vocr_ctc_grammar_beam_search (vistaocr_amd/csrc/ctc_grammar_beam.hip) through ops.ctc_grammar_beam_search and
+"""GPU: vocr_ctc_grammar_beam_search (vistaocr_amd/csrc/ctc_beam.hip, the GRAMMAR instantiation) through ops.ctc_grammar_beam_search and
 GrammarBeamDecoder: against vocr_ctc_beam_search under the automaton that accepts everything (the same bits), against brute force
 where the beam holds every viable prefix, against the fp64 restatement (tests/grammar_beam_ref.py) on dense logits, with per-line
 automata, bad indices and a poisoned table, on a trie beyond the sweep kernels' 8192 cells, and at the corners of the distance rule.

@@ -1,5 +1,7 @@
 // CTC prefix beam search with an optional character n-gram LM: the search side of the reference's decode_with_lm
 // (src/decoder.py:11-109, src/models/cnnlstm.py:298-475), with a character n-gram in ARPA form standing in for the eesen WFST.
+// ONE kernel, template <bool GRAMMAR>, behind two entries: vocr_ctc_beam_search (false) and vocr_ctc_grammar_beam_search (true: the
+// same search over the labellings that a deterministic finite automaton ACCEPTS; "The grammar" below).
 //
 // One workgroup of 256 threads per line; workgroups never talk to each other (no spins, no grid barrier).  Per frame t < lens[b]:
 //   1. row log-softmax of the raw logits in fp32 (one column per thread, V <= 256), then the SYMBOL CLASSES: a class is a
@@ -22,40 +24,87 @@
 //
 // Why stored scores and radix select: the K*V candidate SCORES alone fit in LDS (K = 128, V = 256: 128 KiB; the slot id is the
 // position, so no (score, id) pairs are stored), and four passes over LDS are cheaper than recomputing the candidates (with
-// their LM loads) per pass or merging K sorted per-beam lists.  Static LDS (two beam-state buffers, class log-probs, histogram,
-// selection) is about 20 KiB, so the worst case takes ~148 KiB of the 160 KiB per CU: one line per CU, which is what the
-// problem has (B lines << 256 CUs).
+// their LM loads) per pass or merging K sorted per-beam lists.
 //
 // LM: backoff-resolved dense tables over S states, lm_logp[S][V] (natural log), lm_next[S][V], lm_eos[S]; a candidate costs one
 // load of each, coalesced over c.  State indices read from lm_next outside [0, S) fall back to lm_start (never an out-of-range load).
 // prune_logp: classes whose frame log-prob is below it are not extended (-inf: off, the exact search).
 //
-// Steps 1, 2 (the merge lookup), 4 and the backtrack are the device functions of ctc_beam_common.h, shared with the word search
-// (ctc_word_beam.hip); this file holds the character LM's candidate scoring and beam state.
+// The grammar (GRAMMAR = true).  vocr_ctc_grammar_scores says how probable it is that a line belongs to a regular language and returns
+// the best single PATH; this search sums the paths of each labelling, as the character and word searches do, and keeps only prefixes the
+// automaton can still complete.  Everything above is the same code, so under the one-state automaton that accepts everything the
+// search takes the decisions of vocr_ctc_beam_search, bit for bit.  What `if constexpr (GRAMMAR)` adds, and only there (the false
+// instantiation has none of it, not as a branch either: no state array, no flags, no automaton arguments):
+//   - the automaton is deterministic, so a prefix has exactly ONE state: two beams with the same prefix have the same state and the
+//     exact merge stays valid unchanged.  Each beam carries its LOCAL state (one more int[KMAX] per beam buffer: BeamState<true>).
+//   - line b searches under automaton w = which[b]: rows state_off[w] .. state_off[w+1] of next[states][V] (the local state after
+//     class c, -1: no arc) and dist[states] (the fewest symbols from the state to an accepting one; 0 exactly for the accepting
+//     states, so there is no accept array).
+//   - at frame t with rem = len - 1 - t frames left after it, an extension of beam k by class c is a candidate only if
+//     n = next[state_k][c] is a state of the automaton and 0 <= dist[n] <= rem; a stay only if 0 <= dist[state_k] <= rem.
+//     Every other candidate is -inf, which top_k never takes.  Every further symbol needs a frame of its own, so a prefix that
+//     fails the test has no accepted completion in the frames left: the rule removes only dead prefixes (it is a lower bound: it
+//     ignores the blank a repeated symbol needs, so some dead prefixes stay, but no live one goes).  At the last frame rem = 0 and
+//     only accepting states survive; the final ranking filters on dist == 0 all the same (a line of no frames never gets here).
+//   - the beam may run empty mid-line (the language needs more symbols than there are frames): the frame loop ends and the ranks
+//     stay unfilled.
+// Device contents are never trusted and never become a load address unchecked: which[b] outside [0, g), an empty or reversed state
+// range or one past state_off[g] gives that line no hypothesis; a next state outside the automaton's range is no arc; a negative
+// distance is "cannot accept".  (state_off[g] itself is the size of the two tables and must be right, as lm_states must.)
+//
+// LDS: static 21 056 bytes without the grammar (two beam-state buffers, class log-probs, histogram, selection); with it the beam
+// buffers grow by 2 * 512 bytes and the per-beam viability flags take 512 more: 22 592.  With the worst-case 128 KiB of candidate
+// scores (K = 128, V = 256) that is 152 128 and 153 664 bytes, about 148.6 and 150.1 KiB of the 160 KiB per CU: one line per CU, which
+// is what the problem has (B lines << 256 CUs).
+//
+// Steps 1, 2, 4 and the backtrack are the device functions of ctc_beam_common.h, shared with the word search (ctc_word_beam.hip), as
+// are the host checks of the entries; this file holds the character LM's candidate scoring, the beam state and the grammar.
 #include "ctc_beam_common.h"
 
 namespace {
 
 using namespace ctcbeam;
 
-struct BeamBuf {
+// What the grammar adds to a beam buffer and to the kernel's arguments; both empty without it.
+template <bool GRAMMAR>
+struct BeamState {};
+template <>
+struct BeamState<true> {
+    int gst[KMAX];                              // the beam's local automaton state
+};
+
+template <bool GRAMMAR>
+struct Dfa {};
+template <>
+struct Dfa<true> {
+    const int32_t* __restrict__ state_off;      // [G+1]
+    const int32_t* __restrict__ next;           // [states][V]
+    const int32_t* __restrict__ dist;           // [states]
+    const int32_t* __restrict__ which;          // [B]
+    int G;
+};
+
+template <bool GRAMMAR>
+struct BeamBuf : BeamState<GRAMMAR> {
     float pb[KMAX], pnb[KMAX], acc[KMAX];
     int last[KMAX], len[KMAX], lms[KMAX], node[KMAX];
     unsigned long long hash[KMAX], phash[KMAX];
 };
 
+template <bool GRAMMAR>
 __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ logits, const int32_t* __restrict__ lens, int T, int B,
-                                                      int V, const int32_t* __restrict__ canon, int K, int nbest,
+                                                      int V, const int32_t* __restrict__ canon, int K, int nbest, Dfa<GRAMMAR> D,
                                                       const float* __restrict__ lm_logp, const int32_t* __restrict__ lm_next,
                                                       const float* __restrict__ lm_eos, int S, int lm_start, float alpha, float beta,
                                                       float prune, int32_t* __restrict__ out_labels, int32_t* __restrict__ out_lens,
                                                       float* __restrict__ out_scores, int2* __restrict__ pool_all) {
     extern __shared__ float s_score[];                 // [K*V]
-    __shared__ BeamBuf s_beam[2];
+    __shared__ BeamBuf<GRAMMAR> s_beam[2];
     __shared__ Frame s_f;
     __shared__ Select s_sel;
     __shared__ float s_spb[KMAX], s_spnb[KMAX], s_fin[KMAX];
     __shared__ int s_merge[KMAX];
+    __shared__ int s_ok[KMAX];                         // GRAMMAR: beam j may stay / accepts; never referenced, so not allocated, without
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -64,35 +113,49 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
     const int len_b = min(max(lens[b], 0), T);
     int2* pool = pool_all + (long)b * T * K;
 
+    // GRAMMAR: the line's automaton, rows s0 .. s0 + ns of the tables, or none (the whole workgroup takes the same way)
+    const int32_t* g_next = nullptr;
+    const int32_t* g_dist = nullptr;
+    int ns = 0;
+    if constexpr (GRAMMAR) {
+        const int w = D.which ? D.which[b] : 0;
+        int s0 = 0;
+        if (w >= 0 && w < D.G) {
+            const int total = D.state_off[D.G], lo = D.state_off[w], hi = D.state_off[w + 1];
+            if (lo >= 0 && hi > lo && hi <= total) { s0 = lo; ns = hi - lo; }
+        }
+        if (ns == 0) {
+            if (tid < nbest) write_hyp(b, tid, nbest, T, false, 0, -1, 0.f, 0.f, 0.f, pool, T * K, out_labels, out_lens, out_scores);
+            return;
+        }
+        g_next = D.next + (long)s0 * V;
+        g_dist = D.dist + s0;
+    }
+
     init_classes(canon, V, s_f);
     if (tid == 0) {
-        BeamBuf& B0 = s_beam[0];
+        BeamBuf<GRAMMAR>& B0 = s_beam[0];
         B0.pb[0] = 0.f; B0.pnb[0] = NEG_INF; B0.acc[0] = 0.f; B0.last[0] = -1; B0.len[0] = 0; B0.lms[0] = start;
         B0.node[0] = -1; B0.hash[0] = HASH_ROOT; B0.phash[0] = 0;
+        if constexpr (GRAMMAR) B0.gst[0] = 0;
     }
     int cur = 0, nb = 1;
     __syncthreads();
 
-    for (int t = 0; t < len_b; ++t) {
-        const BeamBuf& C = s_beam[cur];
-        BeamBuf& N = s_beam[cur ^ 1];
+    for (int t = 0; t < len_b && (!GRAMMAR || nb > 0); ++t) {
+        const BeamBuf<GRAMMAR>& C = s_beam[cur];
+        BeamBuf<GRAMMAR>& N = s_beam[cur ^ 1];
+        const int rem = len_b - 1 - t;                 // GRAMMAR: the frames left after this one
         // 1. log-softmax of the row, class log-probs
         frame_logprobs(logits + ((long)t * B + b) * V, V, prune, s_f);
 
-        // 2. stay probabilities and the merge of the extension that re-creates beam j from its parent prefix
+        // 2. stay probabilities and the merge of the extension that re-creates beam j from its parent prefix; whether j may stay
         if (tid < nb) {
-            const int j = tid;
-            const int lj = C.len[j], cj = C.last[j];
-            const int mk = find_merge(j, nb, C.len, C.last, C.node, C.hash, C.phash, s_f.xp, pool, T * K);
-            s_merge[j] = mk;
-            const float pbj = C.pb[j], pnbj = C.pnb[j];
-            float spnb = lj > 0 ? pnbj + s_f.lp[cj] : NEG_INF;
-            if (mk >= 0) {
-                const float base = (cj == C.last[mk]) ? C.pb[mk] : lse2(C.pb[mk], C.pnb[mk]);
-                spnb = lse2(spnb, base + s_f.xp[cj]);
+            stay_and_merge(C, tid, nb, s_f, pool, T * K, s_merge, s_spb, s_spnb);
+            if constexpr (GRAMMAR) {
+                const int dj = g_dist[C.gst[tid]];
+                s_ok[tid] = (dj >= 0 && dj <= rem) ? 1 : 0;
             }
-            s_spb[j] = lse2(pbj, pnbj) + s_f.lp[0];
-            s_spnb[j] = spnb;
         }
         __syncthreads();
 
@@ -104,6 +167,9 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
             if (c == 0) {
                 const float ac = lse2(s_spb[k], s_spnb[k]);
                 sc = ac + (has_lm && alpha != 0.f ? alpha * C.acc[k] : 0.f) + beta * (float)C.len[k];
+                if constexpr (GRAMMAR) {
+                    if (!s_ok[k]) sc = NEG_INF;
+                }
             } else {
                 const float xp = s_f.xp[c];
                 if (xp == NEG_INF) {
@@ -112,6 +178,11 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
                     const float pnb = ((c == C.last[k]) ? C.pb[k] : lse2(C.pb[k], C.pnb[k])) + xp;
                     const float lmv = has_lm ? C.acc[k] + lm_logp[(long)C.lms[k] * V + c] : 0.f;
                     sc = pnb + (has_lm && alpha != 0.f ? alpha * lmv : 0.f) + beta * (float)(C.len[k] + 1);
+                    if constexpr (GRAMMAR) {
+                        const int n = g_next[(long)C.gst[k] * V + c];
+                        const int dn = (n >= 0 && n < ns) ? g_dist[n] : -1;
+                        if (!(dn >= 0 && dn <= rem)) sc = NEG_INF;
+                    }
                 }
             }
             s_score[i] = sc;
@@ -130,18 +201,23 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
             if (c == 0) {
                 N.pb[q] = s_spb[k]; N.pnb[q] = s_spnb[k]; N.acc[q] = C.acc[k]; N.last[q] = C.last[k]; N.len[q] = C.len[k];
                 N.lms[q] = C.lms[k]; N.node[q] = C.node[k]; N.hash[q] = C.hash[k]; N.phash[q] = C.phash[k];
+                if constexpr (GRAMMAR) N.gst[q] = C.gst[k];
             } else {
                 const int node = t * K + q;
                 N.pb[q] = NEG_INF;
                 N.pnb[q] = ((c == C.last[k]) ? C.pb[k] : lse2(C.pb[k], C.pnb[k])) + s_f.xp[c];
                 if (has_lm) {
                     const long e = (long)C.lms[k] * V + c;
-                    const int ns = lm_next[e];
+                    const int ls = lm_next[e];
                     N.acc[q] = C.acc[k] + lm_logp[e];
-                    N.lms[q] = (ns >= 0 && ns < S) ? ns : start;
+                    N.lms[q] = (ls >= 0 && ls < S) ? ls : start;
                 } else {
                     N.acc[q] = 0.f;
                     N.lms[q] = 0;
+                }
+                if constexpr (GRAMMAR) {
+                    const int n = g_next[(long)C.gst[k] * V + c];
+                    N.gst[q] = (n >= 0 && n < ns) ? n : 0;       // a kept candidate has passed the test above
                 }
                 N.last[q] = c; N.len[q] = C.len[k] + 1; N.node[q] = node;
                 N.hash[q] = hash_push(C.hash[k], c); N.phash[q] = C.hash[k];
@@ -153,22 +229,65 @@ __global__ __launch_bounds__(BT) void ctc_beam_kernel(const float* __restrict__ 
         __syncthreads();
     }
 
-    // end of line: + alpha * ln P(</s> | state), final ranking (ties: the rank at the last frame), backtrack the top nbest
-    const BeamBuf& C = s_beam[cur];
+    // end of line: + alpha * ln P(</s> | state), final ranking (ties: the rank at the last frame), backtrack the top nbest.  GRAMMAR:
+    // accepting beams only (a beam that does not accept ranks behind every one that does)
+    const BeamBuf<GRAMMAR>& C = s_beam[cur];
     if (tid < nb) {
         const float lmt = has_lm ? C.acc[tid] + lm_eos[C.lms[tid]] : 0.f;
         s_spb[tid] = lse2(C.pb[tid], C.pnb[tid]);
         s_spnb[tid] = lmt;
-        s_fin[tid] = s_spb[tid] + (has_lm && alpha != 0.f ? alpha * lmt : 0.f) + beta * (float)C.len[tid];
+        const float fin = s_spb[tid] + (has_lm && alpha != 0.f ? alpha * lmt : 0.f) + beta * (float)C.len[tid];
+        if constexpr (GRAMMAR) {
+            const bool accepts = g_dist[C.gst[tid]] == 0;
+            s_ok[tid] = accepts ? 1 : 0;
+            s_fin[tid] = accepts ? fin : __uint_as_float(0x7fc00000u);
+        } else {
+            s_fin[tid] = fin;
+        }
     }
     __syncthreads();
     rank_final(s_fin, nb, s_sel.order);
     if (tid < nbest) {
         const int q = tid;
         const int j = q < nb ? s_sel.order[q] : 0;
-        write_hyp(b, q, nbest, T, q < nb, C.len[j], C.node[j], s_fin[j], s_spb[j], s_spnb[j], pool, T * K, out_labels, out_lens,
+        bool keep = q < nb;
+        if constexpr (GRAMMAR) keep = keep && s_ok[j] != 0;
+        write_hyp(b, q, nbest, T, keep, C.len[j], C.node[j], s_fin[j], s_spb[j], s_spnb[j], pool, T * K, out_labels, out_lens,
                   out_scores);
     }
+}
+
+// the character LM's arguments and the two weights, under the entry's name
+int check_char_lm(const char* who, const float* lm_logp, const int32_t* lm_next, const float* lm_eos, int lm_states, int lm_start,
+                  float lm_weight, float insertion_bonus, float prune_logp) {
+    const bool any_lm = lm_logp || lm_next || lm_eos;
+    VOCR_CHECK_ARG(!any_lm || (lm_logp && lm_next && lm_eos), "%s: lm_logp, lm_next and lm_eos go together", who);
+    VOCR_CHECK_ARG(!any_lm || (lm_states >= 1 && lm_start >= 0 && lm_start < lm_states),
+                   "%s: need 0 <= lm_start < lm_states (lm_start=%d lm_states=%d)", who, lm_start, lm_states);
+    VOCR_CHECK_ARG(__builtin_isfinite(lm_weight) && __builtin_isfinite(insertion_bonus) && !__builtin_isnan(prune_logp),
+                   "%s: lm_weight and insertion_bonus must be finite, prune_logp not NaN", who);
+    return VOCR_OK;
+}
+
+// what both entries do once the automaton, if any, has passed: the checks, the launch of their instantiation
+template <bool GRAMMAR>
+int search(const char* who, size_t need, const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam,
+           int nbest, Dfa<GRAMMAR> D, const float* lm_logp, const int32_t* lm_next, const float* lm_eos, int lm_states, int lm_start,
+           float lm_weight, float insertion_bonus, float prune_logp, int32_t* out_labels, int32_t* out_lens, float* out_scores,
+           void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = check_char_lm(who, lm_logp, lm_next, lm_eos, lm_states, lm_start, lm_weight, insertion_bonus, prune_logp)) return rc;
+    static VocrPerDevice lds_set;
+    if (const int rc = check_search_args(who, logits, lens, t, b, v, beam, nbest, out_labels, out_lens, out_scores, workspace,
+                                         workspace_bytes, need, (const void*)ctc_beam_kernel<GRAMMAR>, &lds_set))
+        return rc;
+    const bool any_lm = lm_logp != nullptr;
+    const size_t lds = (size_t)beam * v * sizeof(float);
+    ctc_beam_kernel<GRAMMAR><<<b, BT, lds, (hipStream_t)stream>>>(logits, lens, t, b, v, canon, beam, nbest, D, lm_logp, lm_next, lm_eos,
+                                                                   any_lm ? lm_states : 1, any_lm ? lm_start : 0, lm_weight,
+                                                                   insertion_bonus, prune_logp, out_labels, out_lens, out_scores,
+                                                                   (int2*)workspace);
+    VOCR_CHECK_LAUNCH(who);
+    return VOCR_OK;
 }
 
 }  // namespace
@@ -178,32 +297,30 @@ extern "C" size_t vocr_ctc_beam_workspace_bytes(int t, int b, int v, int beam, i
     return (size_t)t * b * beam * sizeof(int2);
 }
 
+extern "C" size_t vocr_ctc_grammar_beam_workspace_bytes(int t, int b, int v, int beam, int nbest) {
+    const size_t need = vocr_ctc_beam_workspace_bytes(t, b, v, beam, nbest);
+    if (need == 0 || (long)t * b * beam >= (1L << 31) || (long)t * beam >= (1L << 30)) return 0;
+    return need;
+}
+
 extern "C" int vocr_ctc_beam_search(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam,
                                     int nbest, const float* lm_logp, const int32_t* lm_next, const float* lm_eos, int lm_states,
                                     int lm_start, float lm_weight, float insertion_bonus, float prune_logp, int32_t* out_labels,
                                     int32_t* out_lens, float* out_scores, void* workspace, size_t workspace_bytes, void* stream) {
-    VOCR_CHECK_ARG(logits && lens && out_labels && out_lens && out_scores && workspace, "vocr_ctc_beam_search: null pointer");
-    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 0 && v <= VMAX, "vocr_ctc_beam_search: need t > 0, b > 0, 1 <= v <= %d (t=%d b=%d v=%d)", VMAX,
-                   t, b, v);
-    VOCR_CHECK_ARG(beam >= 1 && beam <= KMAX, "vocr_ctc_beam_search: need 1 <= beam <= %d (beam=%d)", KMAX, beam);
-    VOCR_CHECK_ARG(nbest >= 1 && nbest <= beam, "vocr_ctc_beam_search: need 1 <= nbest <= beam (nbest=%d beam=%d)", nbest, beam);
-    VOCR_CHECK_ARG((long)t * b * beam < (1L << 31) && (long)t * beam < (1L << 30), "vocr_ctc_beam_search: t*b*beam too large");
-    const bool any_lm = lm_logp || lm_next || lm_eos;
-    VOCR_CHECK_ARG(!any_lm || (lm_logp && lm_next && lm_eos), "vocr_ctc_beam_search: lm_logp, lm_next and lm_eos go together");
-    VOCR_CHECK_ARG(!any_lm || (lm_states >= 1 && lm_start >= 0 && lm_start < lm_states),
-                   "vocr_ctc_beam_search: need 0 <= lm_start < lm_states (lm_start=%d lm_states=%d)", lm_start, lm_states);
-    VOCR_CHECK_ARG(__builtin_isfinite(lm_weight) && __builtin_isfinite(insertion_bonus) && !__builtin_isnan(prune_logp),
-                   "vocr_ctc_beam_search: lm_weight and insertion_bonus must be finite, prune_logp not NaN");
-    const size_t need = vocr_ctc_beam_workspace_bytes(t, b, v, beam, nbest);
-    VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_beam_search: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-    static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_beam_kernel};
-    if (vocr_allow_dynamic_lds(big, 1, KMAX * VMAX * (int)sizeof(float), &lds_set, "vocr_ctc_beam_search") != VOCR_OK) return VOCR_ELAUNCH;
-    const size_t lds = (size_t)beam * v * sizeof(float);
-    ctc_beam_kernel<<<b, BT, lds, (hipStream_t)stream>>>(logits, lens, t, b, v, canon, beam, nbest, any_lm ? lm_logp : nullptr, lm_next,
-                                                         lm_eos, any_lm ? lm_states : 1, any_lm ? lm_start : 0, lm_weight,
-                                                         insertion_bonus, prune_logp, out_labels, out_lens, out_scores,
-                                                         (int2*)workspace);
-    VOCR_CHECK_LAUNCH("vocr_ctc_beam_search");
-    return VOCR_OK;
+    return search<false>("vocr_ctc_beam_search", vocr_ctc_beam_workspace_bytes(t, b, v, beam, nbest), logits, lens, t, b, v, canon, beam,
+                         nbest, {}, lm_logp, lm_next, lm_eos, lm_states, lm_start, lm_weight, insertion_bonus, prune_logp, out_labels,
+                         out_lens, out_scores, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vocr_ctc_grammar_beam_search(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam,
+                                            int nbest, const int32_t* g_state_off, const int32_t* dfa_next, const int32_t* dfa_dist, int g,
+                                            const int32_t* which, const float* lm_logp, const int32_t* lm_next, const float* lm_eos,
+                                            int lm_states, int lm_start, float lm_weight, float insertion_bonus, float prune_logp,
+                                            int32_t* out_labels, int32_t* out_lens, float* out_scores, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    VOCR_CHECK_ARG(g_state_off && dfa_next && dfa_dist && which, "vocr_ctc_grammar_beam_search: null automaton table or which");
+    VOCR_CHECK_ARG(g >= 1, "vocr_ctc_grammar_beam_search: need g >= 1 (g=%d)", g);
+    return search<true>("vocr_ctc_grammar_beam_search", vocr_ctc_grammar_beam_workspace_bytes(t, b, v, beam, nbest), logits, lens, t, b, v,
+                        canon, beam, nbest, {g_state_off, dfa_next, dfa_dist, which, g}, lm_logp, lm_next, lm_eos, lm_states, lm_start,
+                        lm_weight, insertion_bonus, prune_logp, out_labels, out_lens, out_scores, workspace, workspace_bytes, stream);
 }

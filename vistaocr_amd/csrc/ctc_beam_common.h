@@ -1,9 +1,11 @@
-// Shared pieces of the two CTC prefix beam searches (ctc_beam.hip: character n-gram, ctc_word_beam.hip: word n-gram + lexicon).
-// One workgroup of BT threads per line; every function here is called by all BT threads of the workgroup (the ones that
-// synchronise say so).  What the kernels share: the symbol classes and their per-frame log-probabilities, the exact merge of an
-// extension into the beam that already holds its prefix, the radix top-K over the K*V candidate scores under the total order
-// (score desc, slot id asc), the final ranking and the backtrack of the n-best from the node pool.  Only integer LDS atomics;
-// every float is computed by a fixed thread in a fixed order.
+// Shared pieces of the CTC prefix beam searches: ctc_beam.hip (one kernel, instantiated without and with a grammar: the character
+// n-gram search and the same search restricted to the labellings an automaton accepts) and ctc_word_beam.hip (word n-gram +
+// lexicon).  One workgroup of BT threads per line; every device function here is called by all BT threads of the workgroup (the
+// ones that synchronise say so) except stay_and_merge, which one thread per beam calls.  What the kernels share: the symbol classes
+// and their per-frame log-probabilities, the stay probabilities with the exact merge of an extension into the beam that already
+// holds its prefix, the radix top-K over the K*V candidate scores under the total order (score desc, slot id asc), the final ranking
+// and the backtrack of the n-best from the node pool; on the host, the argument checks all three entries make.  Only integer LDS
+// atomics; every float is computed by a fixed thread in a fixed order.
 #pragma once
 #include "ctc_math.h"
 
@@ -134,6 +136,25 @@ __device__ __forceinline__ int find_merge(int j, int nb, const int* len, const i
     return mk;
 }
 
+// Step 2 of the frame loop, by thread j < nb: the "stay" probabilities of beam j (spb: after a blank, spnb: after a repeat of its
+// last class, with the extension merged in that re-creates prefix j from the beam merge[j] holding its parent prefix).  Buf is a
+// kernel's beam buffer (pb, pnb, last, len, node, hash, phash); the caller synchronises.
+template <class Buf>
+__device__ __forceinline__ void stay_and_merge(const Buf& C, int j, int nb, const Frame& f, const int2* __restrict__ pool, int npool,
+                                               int* merge, float* spb, float* spnb) {
+    const int lj = C.len[j], cj = C.last[j];
+    const int mk = find_merge(j, nb, C.len, C.last, C.node, C.hash, C.phash, f.xp, pool, npool);
+    merge[j] = mk;
+    const float pbj = C.pb[j], pnbj = C.pnb[j];
+    float s = lj > 0 ? pnbj + f.lp[cj] : NEG_INF;
+    if (mk >= 0) {
+        const float base = (cj == C.last[mk]) ? C.pb[mk] : lse2(C.pb[mk], C.pnb[mk]);
+        s = lse2(s, base + f.xp[cj]);
+    }
+    spb[j] = lse2(pbj, pnbj) + f.lp[0];
+    spnb[j] = s;
+}
+
 struct Select {
     int selid[KMAX], order[KMAX];
     unsigned selkey[KMAX];
@@ -260,6 +281,21 @@ __device__ __forceinline__ void write_hyp(int b, int q, int nbest, int T, bool k
     }
     for (int p = n; p < T; ++p) lab[p] = 0;
     out_lens[(long)b * nbest + q] = n;
+}
+
+// Host: what every search entry checks under its own name `who` once its own arguments have passed - the pointers, the shape, the
+// beam, the pool's index range, the workspace against `need` (the entry's own *_workspace_bytes) - and the opt-in of `kernel` to
+// KMAX * VMAX candidate scores of dynamic LDS (`lds_set`: the entry's own static flags).  VOCR_OK, or the error to return.
+inline int check_search_args(const char* who, const void* logits, const void* lens, int t, int b, int v, int beam, int nbest,
+                             const void* out_labels, const void* out_lens, const void* out_scores, const void* workspace,
+                             size_t workspace_bytes, size_t need, const void* kernel, VocrPerDevice* lds_set) {
+    VOCR_CHECK_ARG(logits && lens && out_labels && out_lens && out_scores && workspace, "%s: null pointer", who);
+    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 0 && v <= VMAX, "%s: need t > 0, b > 0, 1 <= v <= %d (t=%d b=%d v=%d)", who, VMAX, t, b, v);
+    VOCR_CHECK_ARG(beam >= 1 && beam <= KMAX, "%s: need 1 <= beam <= %d (beam=%d)", who, KMAX, beam);
+    VOCR_CHECK_ARG(nbest >= 1 && nbest <= beam, "%s: need 1 <= nbest <= beam (nbest=%d beam=%d)", who, nbest, beam);
+    VOCR_CHECK_ARG((long)t * b * beam < (1L << 31) && (long)t * beam < (1L << 30), "%s: t*b*beam too large", who);
+    VOCR_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    return vocr_allow_dynamic_lds(&kernel, 1, KMAX * VMAX * (int)sizeof(float), lds_set, who);
 }
 
 }  // namespace ctcbeam

@@ -181,20 +181,7 @@ __global__ __launch_bounds__(BT) void ctc_word_beam_kernel(const float* __restri
         WordBeamBuf& N = s_beam[cur ^ 1];
         frame_logprobs(logits + ((long)t * B + b) * V, V, NEG_INF, s_f);
 
-        if (tid < nb) {
-            const int j = tid;
-            const int lj = C.len[j], cj = C.last[j];
-            const int mk = find_merge(j, nb, C.len, C.last, C.node, C.hash, C.phash, s_f.xp, pool, T * K);
-            s_merge[j] = mk;
-            const float pbj = C.pb[j], pnbj = C.pnb[j];
-            float spnb = lj > 0 ? pnbj + s_f.lp[cj] : NEG_INF;
-            if (mk >= 0) {
-                const float base = (cj == C.last[mk]) ? C.pb[mk] : lse2(C.pb[mk], C.pnb[mk]);
-                spnb = lse2(spnb, base + s_f.xp[cj]);
-            }
-            s_spb[j] = lse2(pbj, pnbj) + s_f.lp[0];
-            s_spnb[j] = spnb;
-        }
+        if (tid < nb) stay_and_merge(C, tid, nb, s_f, pool, T * K, s_merge, s_spb, s_spnb);
         __syncthreads();
 
         const int ncand = nb * V;
@@ -291,15 +278,9 @@ extern "C" int vocr_ctc_word_beam_search(const float* logits, const int32_t* len
                                          int lm_start, int tok_unk, int tok_eos, float lm_weight, float word_bonus, float oov_penalty,
                                          int32_t* out_labels, int32_t* out_lens, float* out_scores, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-    VOCR_CHECK_ARG(logits && lens && out_labels && out_lens && out_scores && workspace, "vocr_ctc_word_beam_search: null pointer");
     VOCR_CHECK_ARG(cls_kind && cls_tok && trie_next && trie_tok && trie_la && lm_off && lm_succ_tok && lm_succ_logp && lm_succ_next &&
                        lm_bow && lm_back,
                    "vocr_ctc_word_beam_search: null table pointer");
-    VOCR_CHECK_ARG(t > 0 && b > 0 && v > 0 && v <= VMAX, "vocr_ctc_word_beam_search: need t > 0, b > 0, 1 <= v <= %d (t=%d b=%d v=%d)",
-                   VMAX, t, b, v);
-    VOCR_CHECK_ARG(beam >= 1 && beam <= KMAX, "vocr_ctc_word_beam_search: need 1 <= beam <= %d (beam=%d)", KMAX, beam);
-    VOCR_CHECK_ARG(nbest >= 1 && nbest <= beam, "vocr_ctc_word_beam_search: need 1 <= nbest <= beam (nbest=%d beam=%d)", nbest, beam);
-    VOCR_CHECK_ARG((long)t * b * beam < (1L << 31) && (long)t * beam < (1L << 30), "vocr_ctc_word_beam_search: t*b*beam too large");
     VOCR_CHECK_ARG(trie_nodes >= 1 && lm_states >= 1 && lm_tokens >= 1 && lm_succ >= lm_tokens,
                    "vocr_ctc_word_beam_search: need trie_nodes >= 1, lm_states >= 1, lm_tokens >= 1, lm_succ >= lm_tokens "
                    "(trie_nodes=%d lm_states=%d lm_tokens=%d lm_succ=%d)",
@@ -311,12 +292,11 @@ extern "C" int vocr_ctc_word_beam_search(const float* logits, const int32_t* len
     VOCR_CHECK_ARG((long)trie_nodes * v < (1L << 31), "vocr_ctc_word_beam_search: trie_nodes*v too large");
     VOCR_CHECK_ARG(__builtin_isfinite(lm_weight) && __builtin_isfinite(word_bonus) && !__builtin_isnan(oov_penalty) && oov_penalty < INFINITY,
                    "vocr_ctc_word_beam_search: lm_weight and word_bonus must be finite, oov_penalty finite or -inf");
-    const size_t need = vocr_ctc_word_beam_workspace_bytes(t, b, v, beam, nbest);
-    VOCR_CHECK_ARG(workspace_bytes >= need, "vocr_ctc_word_beam_search: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
     static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_word_beam_kernel};
-    if (vocr_allow_dynamic_lds(big, 1, KMAX * VMAX * (int)sizeof(float), &lds_set, "vocr_ctc_word_beam_search") != VOCR_OK)
-        return VOCR_ELAUNCH;
+    if (const int rc = check_search_args("vocr_ctc_word_beam_search", logits, lens, t, b, v, beam, nbest, out_labels, out_lens, out_scores,
+                                         workspace, workspace_bytes, vocr_ctc_word_beam_workspace_bytes(t, b, v, beam, nbest),
+                                         (const void*)ctc_word_beam_kernel, &lds_set))
+        return rc;
     WordLm L;
     L.kind = cls_kind; L.tok = cls_tok; L.trie_next = trie_next; L.trie_tok = trie_tok; L.trie_la = trie_la;
     L.off = lm_off; L.succ_tok = lm_succ_tok; L.succ_logp = lm_succ_logp; L.succ_next = lm_succ_next; L.bow = lm_bow; L.back = lm_back;

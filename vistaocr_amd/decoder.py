@@ -99,67 +99,86 @@ class ArgmaxDecoder:
         return _alternatives(model_output, lens_dev, labels.unsqueeze(1), counts.unsqueeze(1), None, canon, alphabet, uxxxx, topk)
 
 
-class BeamDecoder:
+class _SearchDecoder:
+    """What the three beam-search decoders share: the beam limits, the alphabet's symbol classes on each device, and the output formats
+    of one search.  A decoder adds its constructor and _search_device(model_output, batch_actual_timesteps, nbest, ...) -> the device
+    tensors (labels [B,nbest,T], lengths [B,nbest], scores [B,nbest,3]) of its ops.ctc_*_search; what a public method gets beyond its
+    own arguments goes to _search_device as it came (GrammarBeamDecoder: which=)."""
+
+    def __init__(self, alphabet, beam, nbest):
+        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
+            raise ValueError("%s: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (type(self).__name__, beam, nbest))
+        self.alphabet = alphabet
+        self.beam, self.nbest = int(beam), int(nbest)
+        self._canon = {}
+
+    def _canon_on(self, dev):
+        """(the alphabet's canonical indices as an int32 tensor on `dev`, made once per device; whether this call made it)"""
+        key = str(dev)
+        new = key not in self._canon
+        if new:
+            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
+        return self._canon[key], new
+
+    def _search(self, model_output, batch_actual_timesteps, nbest, *more, **kw):
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest, *more, **kw)
+        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
+
+    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1, *more, **kw):
+        """(hypotheses as decode() returns them, alignments): the search, then vocr_ctc_align on its device outputs, one device-to-host
+        copy at the end.  nbest = 1: per line the LineAlignment (vistaocr_amd.align) of the best hypothesis, None where the search
+        found none.  nbest > 1: per line a list of (labels, (total, acoustic, lm), LineAlignment), best first, as decode_nbest lists
+        them.  An alignment's ctc_logp is the full forward score of the labelling; the search's acoustic score sums only the paths its
+        beam kept, so it is a lower bound of it and equals it when the beam pruned nothing of weight."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest), *more, **kw)
+        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
+
+    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False, *more, **kw):
+        """(hypotheses as decode() returns them, per line a LineAlternatives of the best hypothesis, None where the search found none):
+        the search, then vocr_ctc_edit_scores on its device outputs, one device-to-host copy at the end.  The posteriors
+        (CtcAligner.alternatives says what they are) are those of the CTC model alone: the LM and the grammar rank the search, not the
+        edits, so an alternative may leave the grammar's language."""
+        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1, *more, **kw)
+        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
+                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
+
+    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None, *more, **kw):
+        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first, an empty list where the search found none;
+        labels are canonical alphabet indices, acoustic the CTC log-probability of the labelling, lm the LM log-probability including
+        </s> (0 without an LM; WordBeamDecoder: of the tokens, and a line whose every beam ends inside a word that cannot close has no
+        hypothesis; GrammarBeamDecoder: every labelling is accepted by the line's grammar)."""
+        nbest = self.nbest if nbest is None else int(nbest)
+        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest, *more, **kw))
+
+    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None, *more, **kw):
+        """The best hypothesis of each line in decode_greedy's format: space-joined uxxxx tokens, converted to utf8 unless uxxxx ("" for
+        a line without one)."""
+        if lang is not None:
+            raise ValueError("%s: one alphabet per decoder (lang is not supported)" % type(self).__name__)
+        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1, *more, **kw), self.alphabet, uxxxx)
+
+
+class BeamDecoder(_SearchDecoder):
     """CTC prefix beam search on the GPU (vocr_ctc_beam_search), optionally with a character n-gram LM (vistaocr_amd.lm.CharNgramLM):
     the stand-in for the reference's LM decode (decode_with_lm, src/decoder.py:11-109).  Hypotheses are ranked by
     ln P_ctc(y | x) + lm_weight * ln P_lm(y </s>) + insertion_bonus * |y|; `prune_logp` (None: off) skips extensions by symbols whose
     frame log-probability is below it.  Symbols with the same alphabet string are one symbol, as in the greedy decode."""
 
     def __init__(self, alphabet, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None):
-        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
-            raise ValueError("BeamDecoder: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (beam, nbest))
+        super().__init__(alphabet, beam, nbest)
         if lm is not None and lm.logp.shape[1] != len(alphabet):
             raise ValueError("BeamDecoder: the LM was resolved for %d symbols, the alphabet has %d" % (lm.logp.shape[1], len(alphabet)))
-        self.alphabet = alphabet
-        self.beam, self.nbest = int(beam), int(nbest)
         self.lm, self.lm_weight, self.insertion_bonus, self.prune_logp = lm, float(lm_weight), float(insertion_bonus), prune_logp
-        self._canon = {}
 
     def _search_device(self, model_output, batch_actual_timesteps, nbest):
         dev = model_output.device
-        key = str(dev)
-        if key not in self._canon:
-            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
-        return ops.ctc_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key], self.beam, nbest,
+        return ops.ctc_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon_on(dev)[0], self.beam, nbest,
                                    self.lm.to(dev) if self.lm is not None else None, self.lm_weight, self.insertion_bonus,
                                    self.prune_logp)
 
-    def _search(self, model_output, batch_actual_timesteps, nbest):
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest)
-        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
 
-    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1):
-        """(hypotheses as decode() returns them, alignments): the search, then vocr_ctc_align on its device outputs, one device-to-host
-        copy at the end.  nbest = 1: per line the LineAlignment (vistaocr_amd.align) of the best hypothesis, None where the search
-        found none.  nbest > 1: per line a list of (labels, (total, acoustic, lm), LineAlignment), best first, as decode_nbest lists
-        them.  An alignment's ctc_logp is the full forward score of the labelling; the search's acoustic score sums only the paths its
-        beam kept, so it is a lower bound of it and equals it when the beam pruned nothing of weight."""
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest))
-        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
-                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
-
-    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False):
-        """(hypotheses as decode() returns them, per line a LineAlternatives of the best hypothesis, None where the search found none):
-        the search, then vocr_ctc_edit_scores on its device outputs, one device-to-host copy at the end.  The posteriors
-        (CtcAligner.alternatives says what they are) are those of the CTC model alone: the LM ranks the search, not the edits."""
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1)
-        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
-                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
-
-    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
-        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; labels are canonical alphabet indices,
-        acoustic the CTC log-probability of the labelling, lm the LM log-probability including </s> (0 without an LM)."""
-        nbest = self.nbest if nbest is None else int(nbest)
-        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest))
-
-    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
-        """The best hypothesis of each line in decode_greedy's format: space-joined uxxxx tokens, converted to utf8 unless uxxxx."""
-        if lang is not None:
-            raise ValueError("BeamDecoder: one alphabet per decoder (lang is not supported)")
-        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1), self.alphabet, uxxxx)
-
-
-class GrammarBeamDecoder:
+class GrammarBeamDecoder(_SearchDecoder):
     """Grammar-constrained CTC prefix beam search on the GPU (vocr_ctc_grammar_beam_search): what the line READS, given that it is a
     date, an amount or one of these part numbers.  BeamDecoder's search, LM, ranking and output formats, restricted to the labellings a
     Grammar (vistaocr_amd.grammar) accepts: each beam carries its automaton state, and a prefix that the frames left cannot complete
@@ -171,8 +190,7 @@ class GrammarBeamDecoder:
 
     def __init__(self, alphabet, grammars, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None,
                  max_table_bytes=1 << 30):
-        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
-            raise ValueError("GrammarBeamDecoder: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (beam, nbest))
+        super().__init__(alphabet, beam, nbest)
         if lm is not None and lm.logp.shape[1] != len(alphabet):
             raise ValueError("GrammarBeamDecoder: the LM was resolved for %d symbols, the alphabet has %d"
                              % (lm.logp.shape[1], len(alphabet)))
@@ -183,57 +201,24 @@ class GrammarBeamDecoder:
             if len(g.alphabet) != len(alphabet):
                 raise ValueError("GrammarBeamDecoder: %s is over an alphabet of %d symbols, the decoder's has %d"
                                  % (g.name, len(g.alphabet), len(alphabet)))
-        self.alphabet = alphabet
-        self.beam, self.nbest = int(beam), int(nbest)
         self.lm, self.lm_weight, self.insertion_bonus, self.prune_logp = lm, float(lm_weight), float(insertion_bonus), prune_logp
         self.max_table_bytes = int(max_table_bytes)
-        self._canon, self._packed = {}, {}
+        self._packed = {}
 
     def _search_device(self, model_output, batch_actual_timesteps, nbest, which=None):
         dev = model_output.device
-        key = str(dev)
-        if key not in self._canon:
-            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
-            self._packed[key] = pack_dense_grammars(self.grammars, dev, self.max_table_bytes)
+        canon, new = self._canon_on(dev)
+        if new:
+            self._packed[str(dev)] = pack_dense_grammars(self.grammars, dev, self.max_table_bytes)
         if which is not None:
             which = [int(k) for k in (which.tolist() if torch.is_tensor(which) else which)]
             if len(which) != int(model_output.shape[1]):
                 raise ValueError("GrammarBeamDecoder: %d entries of which for %d lines" % (len(which), int(model_output.shape[1])))
             if min(which) < 0 or max(which) >= len(self.grammars):
                 raise ValueError("GrammarBeamDecoder: which must index the %d grammars" % len(self.grammars))
-        return ops.ctc_grammar_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._packed[key], which,
-                                           self._canon[key], self.beam, nbest, self.lm.to(dev) if self.lm is not None else None,
+        return ops.ctc_grammar_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._packed[str(dev)], which,
+                                           canon, self.beam, nbest, self.lm.to(dev) if self.lm is not None else None,
                                            self.lm_weight, self.insertion_bonus, self.prune_logp)
-
-    def _search(self, model_output, batch_actual_timesteps, nbest, which=None):
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest, which)
-        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
-
-    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1, which=None):
-        """BeamDecoder.decode_aligned for the grammar search: (hypotheses, alignments)."""
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest), which)
-        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
-                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
-
-    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False, which=None):
-        """BeamDecoder.decode_alternatives for the grammar search: (hypotheses, per line a LineAlternatives of the best hypothesis, None
-        where the search found none).  The posteriors are those of the CTC model alone: the grammar and the LM rank the search, not the
-        edits, so an alternative may leave the language."""
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1, which)
-        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
-                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
-
-    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None, which=None):
-        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first, every one accepted by the line's grammar; an
-        empty list where the search found none."""
-        nbest = self.nbest if nbest is None else int(nbest)
-        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest, which))
-
-    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None, which=None):
-        """The best accepted hypothesis of each line in decode_greedy's format ("" for a line without one)."""
-        if lang is not None:
-            raise ValueError("GrammarBeamDecoder: one alphabet per decoder (lang is not supported)")
-        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1, which), self.alphabet, uxxxx)
 
 
 def _line_lengths(batch_actual_timesteps):
@@ -293,7 +278,7 @@ def _best_strings(labels, lengths, scores, alphabet, uxxxx):
     return result
 
 
-class WordBeamDecoder:
+class WordBeamDecoder(_SearchDecoder):
     """CTC prefix beam search on the GPU scored by a word n-gram with a lexicon (vocr_ctc_word_beam_search, WordNgramLM): the stand-in
     for the reference's TLG.fst decode (decode_with_lm, src/decoder.py:11-109).  Hypotheses are ranked by ln P_ctc(y | x) +
     lm_weight * ln P_lm(tokens of y, </s>) + word_bonus * |tokens of y|, the tokens those of form_tokenized_words.  Letter-words are
@@ -301,50 +286,14 @@ class WordBeamDecoder:
     penalty.  Output formats as BeamDecoder's."""
 
     def __init__(self, alphabet, lm, beam=16, nbest=1, lm_weight=0.8, word_bonus=0.0, oov_penalty=None):
-        if not 1 <= int(beam) <= 128 or not 1 <= int(nbest) <= int(beam):
-            raise ValueError("WordBeamDecoder: need 1 <= nbest <= beam <= 128 (beam=%s nbest=%s)" % (beam, nbest))
+        super().__init__(alphabet, beam, nbest)
         if lm.trie_next.shape[1] != len(alphabet):
             raise ValueError("WordBeamDecoder: the LM was resolved for %d symbols, the alphabet has %d" % (lm.trie_next.shape[1], len(alphabet)))
-        self.alphabet, self.lm = alphabet, lm
-        self.beam, self.nbest = int(beam), int(nbest)
+        self.lm = lm
         self.lm_weight, self.word_bonus = float(lm_weight), float(word_bonus)
         self.oov_penalty = None if oov_penalty is None else float(oov_penalty)
-        self._canon = {}
 
     def _search_device(self, model_output, batch_actual_timesteps, nbest):
         dev = model_output.device
-        key = str(dev)
-        if key not in self._canon:
-            self._canon[key] = torch.as_tensor(self.alphabet.canonical_indices(), dtype=torch.int32).to(dev)
-        return ops.ctc_word_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon[key], self.lm.to(dev),
-                                        self.beam, nbest, self.lm_weight, self.word_bonus, self.oov_penalty)
-
-    def _search(self, model_output, batch_actual_timesteps, nbest):
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, nbest)
-        return labels.cpu().numpy(), lengths.cpu().numpy(), scores.cpu().numpy()
-
-    def decode_aligned(self, model_output, batch_actual_timesteps, uxxxx=False, nbest=1):
-        """BeamDecoder.decode_aligned for the word search: (hypotheses, alignments)."""
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, int(nbest))
-        return _aligned(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
-                        self._canon[str(model_output.device)], self.alphabet, uxxxx, int(nbest))
-
-    def decode_alternatives(self, model_output, batch_actual_timesteps, topk=3, uxxxx=False):
-        """(hypotheses as decode() returns them, per line a LineAlternatives of the best hypothesis, None where the search found none):
-        the search, then vocr_ctc_edit_scores on its device outputs, one device-to-host copy at the end.  The posteriors
-        (CtcAligner.alternatives says what they are) are those of the CTC model alone: the LM ranks the search, not the edits."""
-        labels, lengths, scores = self._search_device(model_output, batch_actual_timesteps, 1)
-        return _alternatives(model_output, _line_lengths(batch_actual_timesteps), labels, lengths, scores,
-                             self._canon[str(model_output.device)], self.alphabet, uxxxx, topk)
-
-    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None):
-        """Per line, a list of up to `nbest` (labels, (total, acoustic, lm)) best first; lm is the word LM's log-probability of the
-        tokens including </s>.  A line whose every beam ends inside a word that cannot close has no hypothesis."""
-        nbest = self.nbest if nbest is None else int(nbest)
-        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest))
-
-    def decode(self, model_output, batch_actual_timesteps, uxxxx=False, lang=None):
-        """The best hypothesis of each line in decode_greedy's format ("" for a line without one)."""
-        if lang is not None:
-            raise ValueError("WordBeamDecoder: one alphabet per decoder (lang is not supported)")
-        return _best_strings(*self._search(model_output, batch_actual_timesteps, 1), self.alphabet, uxxxx)
+        return ops.ctc_word_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._canon_on(dev)[0],
+                                        self.lm.to(dev), self.beam, nbest, self.lm_weight, self.word_bonus, self.oov_penalty)

@@ -1279,15 +1279,18 @@ def clamp_(x, clamp):
     return x
 
 
+def _line_ints(vals, dev):
+    """One int per line (any int sequence or tensor) as an int32 tensor on `dev`."""
+    if torch.is_tensor(vals):
+        return vals.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.as_tensor([int(v) for v in vals], dtype=torch.int32).to(dev)
+
+
 def _lens_canon(what, logits, lens, canon):
     """What every CTC entry over raw logits [T,B,V] does with `lens` (any int sequence or tensor: the frames of each line) and `canon`
     (int32 [V] device tensor of the symbol classes or None): returns lens as an int32 device tensor of B entries, and checks canon."""
     _, B, V = logits.shape
-    dev = logits.device
-    if torch.is_tensor(lens):
-        lens_dev = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_dev = torch.as_tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    lens_dev = _line_ints(lens, logits.device)
     if lens_dev.numel() != B:
         raise RuntimeError("%s: %d lengths for %d lines" % (what, lens_dev.numel(), B))
     if canon is not None:
@@ -1295,6 +1298,25 @@ def _lens_canon(what, logits, lens, canon):
         if canon.dtype != torch.int32 or canon.numel() != V:
             raise RuntimeError("%s: canon must be int32 [V]" % what)
     return lens_dev
+
+
+def _search_outputs(B, nbest, T, dev):
+    """What every beam search returns: labels int32 [B,nbest,T], lengths int32 [B,nbest], scores fp32 [B,nbest,3]."""
+    return (torch.empty(B, nbest, T, dtype=torch.int32, device=dev), torch.empty(B, nbest, dtype=torch.int32, device=dev),
+            torch.empty(B, nbest, 3, dtype=torch.float32, device=dev))
+
+
+def _char_lm_args(what, lm, V):
+    """The character LM's five C arguments from `lm` (CharNgramLM.to(device), or None: no LM), its tables checked against V."""
+    if lm is None:
+        return (None, None, None, 0, 0)
+    lp, nx, eos = lm["lm_logp"], lm["lm_next"], lm["lm_eos"]
+    _need_gpu(lp, nx, eos)
+    S = lp.shape[0]
+    if lp.shape != (S, V) or nx.shape != (S, V) or eos.shape != (S,) or lp.dtype != torch.float32 or nx.dtype != torch.int32:
+        raise RuntimeError("%s: LM tables do not match V=%d (lm_logp %s, lm_next %s, lm_eos %s)"
+                           % (what, V, tuple(lp.shape), tuple(nx.shape), tuple(eos.shape)))
+    return (_p(lp), _p(nx), _p(eos), S, int(lm["start"]))
 
 
 def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None):
@@ -1312,20 +1334,9 @@ def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weig
         raise RuntimeError("ctc_beam_search: unsupported shape or beam (T=%d B=%d V=%d beam=%d nbest=%d; V <= 256, 1 <= nbest <= beam "
                            "<= 128)" % (T, B, V, beam, nbest))
     lens_dev = _lens_canon("ctc_beam_search", logits, lens, canon)
-    labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
+    labels, out_lens, scores = _search_outputs(B, nbest, T, dev)
     ws = _ws(nbytes, dev)
-    if lm is not None:
-        lp, nx, eos = lm["lm_logp"], lm["lm_next"], lm["lm_eos"]
-        _need_gpu(lp, nx, eos)
-        S = lp.shape[0]
-        if lp.shape != (S, V) or nx.shape != (S, V) or eos.shape != (S,) or lp.dtype != torch.float32 or nx.dtype != torch.int32:
-            raise RuntimeError("ctc_beam_search: LM tables do not match V=%d (lm_logp %s, lm_next %s, lm_eos %s)"
-                               % (V, tuple(lp.shape), tuple(nx.shape), tuple(eos.shape)))
-        lm_args = (_p(lp), _p(nx), _p(eos), S, int(lm["start"]))
-    else:
-        lm_args = (None, None, None, 0, 0)
+    lm_args = _char_lm_args("ctc_beam_search", lm, V)
     prune = float("-inf") if prune_logp is None else float(prune_logp)
     call("vocr_ctc_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), *lm_args, float(lm_weight),
          float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores), _p(ws), ws.numel() * 4, _stream())
@@ -1358,28 +1369,12 @@ def ctc_grammar_beam_search(logits, lens, dense_packed, which=None, canon=None, 
             or not (s_off.is_contiguous() and nxt.is_contiguous() and dist.is_contiguous())):
         raise RuntimeError("ctc_grammar_beam_search: the dense tables do not match V=%d (state_off %s %s, next %s %s, dist %s %s)"
                            % (V, tuple(s_off.shape), s_off.dtype, tuple(nxt.shape), nxt.dtype, tuple(dist.shape), dist.dtype))
-    if which is None:
-        which_dev = torch.zeros(B, dtype=torch.int32, device=dev)
-    elif torch.is_tensor(which):
-        which_dev = which.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        which_dev = torch.as_tensor([int(k) for k in which], dtype=torch.int32).to(dev)
+    which_dev = torch.zeros(B, dtype=torch.int32, device=dev) if which is None else _line_ints(which, dev)
     if which_dev.numel() != B:
         raise RuntimeError("ctc_grammar_beam_search: %d entries of which for %d lines" % (which_dev.numel(), B))
-    labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
+    labels, out_lens, scores = _search_outputs(B, nbest, T, dev)
     ws = _ws(nbytes, dev)
-    if lm is not None:
-        lp, nx, eos = lm["lm_logp"], lm["lm_next"], lm["lm_eos"]
-        _need_gpu(lp, nx, eos)
-        S = lp.shape[0]
-        if lp.shape != (S, V) or nx.shape != (S, V) or eos.shape != (S,) or lp.dtype != torch.float32 or nx.dtype != torch.int32:
-            raise RuntimeError("ctc_grammar_beam_search: LM tables do not match V=%d (lm_logp %s, lm_next %s, lm_eos %s)"
-                               % (V, tuple(lp.shape), tuple(nx.shape), tuple(eos.shape)))
-        lm_args = (_p(lp), _p(nx), _p(eos), S, int(lm["start"]))
-    else:
-        lm_args = (None, None, None, 0, 0)
+    lm_args = _char_lm_args("ctc_grammar_beam_search", lm, V)
     prune = float("-inf") if prune_logp is None else float(prune_logp)
     call("vocr_ctc_grammar_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(s_off), _p(nxt), _p(dist),
          G, _p(which_dev), *lm_args, float(lm_weight), float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores), _p(ws),
@@ -1418,9 +1413,7 @@ def ctc_word_beam_search(logits, lens, canon, lm, beam=16, nbest=1, lm_weight=0.
         raise RuntimeError("ctc_word_beam_search: word LM tables do not match V=%d (bad dtype or layout: %s; kind %s, trie_next %s, "
                            "off %s, bow %s, succ_tok %s)" % (V, bad, tuple(lm["kind"].shape), tuple(lm["trie_next"].shape),
                                                              tuple(lm["off"].shape), tuple(lm["bow"].shape), tuple(lm["succ_tok"].shape)))
-    labels = torch.empty(B, nbest, T, dtype=torch.int32, device=dev)
-    out_lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, nbest, 3, dtype=torch.float32, device=dev)
+    labels, out_lens, scores = _search_outputs(B, nbest, T, dev)
     ws = _ws(nbytes, dev)
     oov = float("-inf") if oov_penalty is None else float(oov_penalty)
     call("vocr_ctc_word_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(lm["kind"]), _p(lm["tok"]),
