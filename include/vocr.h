@@ -270,8 +270,11 @@ int vocr_dropout_mask(float* mask, size_t count, float p, uint64_t seed, void* s
 /* ---- nn.LSTM recurrence on a packed, length-sorted batch — src/models/cnnlstm.py:148-149,288-290 ---------- */
 /* One direction pair of one layer.  xproj[dir][T][B][4H] = x W_ih^T + b_ih + b_hh (gate order i,f,g,o),
  * whh_fwd / whh_rev [4H][H] (the two directions' weight_hh), lens[B] int32 (device, descending).  Outputs y[T][B][2H] (zeros past lens),
- * gates[dir][T][B][H][4] (post-activation i,f,g,o interleaved per unit, 16-byte aligned) and cell[dir][T][B][H]
- * for backward.  h_{t-1}/c_{t-1} are read back from y/cell, so the sweep keeps no separate state.
+ * gates[dir][T][B][H][4] (post-activation i,f,g,o interleaved per unit) and cell[dir][T][B][H] for backward.  The forward writes EVERY
+ * frame of gates and cell, zeros past lens (the caller need not clear them), and the backward entries never read a frame past lens.
+ * gates must be 16-byte aligned in every entry that takes it, forward and backward (each unit's four gates move as one 16-byte
+ * piece): a call with another pointer fails with VOCR_EINVAL before any launch.  whh_*, y, whht_* and dgates may have any float alignment (the
+ * sweeps then run one generic launch per step).  h_{t-1}/c_{t-1} are read back from y/cell, so the sweep keeps no separate state.
  * workspace: vocr_lstm_workspace_bytes (256-byte aligned device memory; contents need not be preserved between calls, except
  * between the vocr_lstm_fwd_range calls of ONE sweep: the forward sweep's hand-off buffer lives there).
  * Supports B <= 64 per call, H % 16 == 0 (a larger batch is several calls on batch tiles: the recurrence never couples batch rows and
@@ -390,7 +393,8 @@ int vocr_gemm_h3_two_views(const void* a_planes, int a_rows, int a_k, int a_row0
  * All GEMMs of the LSTM stack then run over `rows` rows instead of T*B, the recurrent weight gradient is still ONE product of
  * row-shifted views (shift 4: the all-zero group in front of / behind a chain is its h_{-1} / h_{L_c}), and a chain's workgroups leave
  * a sweep after their own L_c steps.  Contract: the caller zero-fills y before vocr_lstm_fwd_packed and dgates before
- * vocr_lstm_bwd_packed (the zero groups, a last chain's rows >= B and nothing else stay untouched by the sweeps); rows of a chain past
+ * vocr_lstm_bwd_packed (the zero groups, a last chain's rows >= B and nothing else stay untouched by the sweeps: in gates and cell
+ * these rows keep whatever they held, and nothing a sweep writes depends on them or on the same rows of xproj, dy and dy_mask); rows of a chain past
  * their own length are written as zeros like in the dense layout.  Results per frame are those of the dense entry points (same
  * kernels, same summation orders).  Shapes: ask vocr_lstm_packed_supported (B <= 32, H in {256, 512} on a device that can hold the
  * persistent sweep's grid) and keep rows * 2H * 4 below 2 GB (the sweeps' 32-bit offsets); otherwise use the dense entry points above.

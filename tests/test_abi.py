@@ -84,6 +84,8 @@ def test_argument_validation_without_gpu():
     one = ctypes.c_void_p(16)
     rc = lib.vocr_gemm_pair(0, 0, 0, 256, 256, 64, one, one, 8, one, one, 256, one, one, 256, None, None, 0, None, 0, None)
     assert rc == -1 and b"leading dimension" in lib.vocr_last_error()
+    # gates is loaded 16 bytes at a time by every backward kernel: a pointer 4 bytes off is refused next to the shape check
+    assert lib.vocr_lstm_bwd(one, one, one, one, ctypes.c_void_p(20), one, one, one, 4, 4, 16, None, None) == -1 and b"vocr_lstm_bwd: gates must be 16-byte aligned" in lib.vocr_last_error()
     assert lib.vocr_conv3x3_wgrad_workspace_bytes(32, 256, 7, 294, 256) > 0
     assert lib.vocr_ctc_workspace_bytes(294, 32, 96, 20) > 0
     # round 5 entry points: shape answers that need no device, and argument validation in front of any launch

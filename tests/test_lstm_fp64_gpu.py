@@ -13,11 +13,11 @@ import pytest
 import torch
 
 from tests import lstm_ref as lr
+from tests.lstm_cases import _ALL, SETTINGS, _ragged, case, make_inputs, sweep_kind          # noqa: F401 (shared with the guarded suite)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CUS = 256          # MI355X compute units: resident_workgroup_capacity() of lstm.hip
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -29,32 +29,7 @@ def _cpu_threads():
     torch.set_num_threads(n)
 
 
-def sweep_kind(backward, B, H, floor, rows=None, cap=CUS):
-    """lstm_sweep_kind of lstm.hip (the table at its head) for floor = VOCR_LSTM_SWEEP: wide4 < chain4 < chain16 < step."""
-    order = ("wide4", "chain4", "chain16", "step")
-    fl = order.index(floor)
-    if backward:
-        ok = H in (128, 256, 512) and 8 * (H // 16) <= cap
-    else:
-        ok = H in (64, 128, 256, 512) and (rows if rows else 0) * 2 * H * 4 < 2 ** 31 and 8 * (H // 16) <= cap
-    if not ok or fl == 3:
-        return "step"
-    nt4 = (B + 3) // 4
-    if fl <= 0 and H == 512 and 4 < nt4 <= 8 and 256 <= cap:
-        return "wide4"
-    if fl <= 1 and 2 * nt4 <= 16 and H in (256, 512) and (16 if 2 * nt4 > 8 else 8) * (H // 16) <= 2 * cap:
-        return "chain4"
-    return "chain16"
-
-
-def _ragged(T, B):
-    """descending, first T, last 1"""
-    if B == 1:
-        return [T]
-    return sorted([max(1, T - (T * i) // (B - 1)) for i in range(B)], reverse=True)
-
-
-# (T, B, H, lens, regimes, floors): what each (shape, floor) pair reaches, forward / backward, by the rule (sweep_kind above):
+# (T, B, H, lens, regimes, floors): what each (shape, floor) pair reaches, forward / backward, by the rule (sweep_kind of tests/lstm_cases.py):
 #   294 x 32 x 512         wide4: wide4/wide4    chain4: chain4/chain4    chain16: chain16/chain16   step: step/step   (the bench shape)
 #   588 x 32 x 512         wide4 and step only (configs[3]'s long ragged line)
 #   60 x 17 x 512          wide4: wide4/wide4    chain4: chain4/chain4    chain16: chain16/chain16 (the wide4 lower boundary)
@@ -65,7 +40,6 @@ def _ragged(T, B):
 #   40 x 48 x 64           every floor but step: chain16 forward / step backward (no backward fast path below H = 128)
 #   30 x 5 x 48, 20 x 3 x 16, 12 x 4 x 1024: step/step (the generic per-step kernels) at every floor
 #   1 x 1 x 256            wide4, chain4: chain4/chain4;  2 x 3 x 512: the same (T = 1, T = 2, B = 1)
-_ALL = ("wide4", "chain4", "chain16", "step")
 CASES = [
     (294, 32, 512, "full", ("ref",), _ALL),
     (294, 32, 512, "ragged", ("ref",), _ALL),
@@ -83,57 +57,6 @@ CASES = [
     (1, 1, 256, "full", ("ref", "sat"), _ALL),
     (2, 3, 512, "ragged", ("ref", "sat"), _ALL),
 ]
-# every setting of the library's two switches (one child each); write-through only changes the persistent kinds
-SETTINGS = ("step", "wide4", "chain4", "chain16", "wide4/wt", "chain4/wt", "chain16/wt")
-
-
-def make_inputs(T, B, H, lens, regime, seed):
-    """fp32 inputs of one case (the kernels' own values; the references read them exactly): xproj [2][T][B][4H], W_hh [2][4H][H],
-    dy [T][B][2H], dy_mask [T][B][2H] (0 or 2: dy * mask is exact in fp32, so vocr_lstm_bwd_bias on the product and vocr_lstm_bwd_parts on
-    the pair answer to one reference)."""
-    g = torch.Generator().manual_seed(seed)
-
-    def u(*s):
-        return torch.rand(*s, generator=g) * 2 - 1
-
-    if regime == "ref":                       # the reference model's init scale
-        xproj, whh = u(2, T, B, 4 * H) * 0.5, u(2, 4 * H, H) * 0.08
-    elif regime == "sat":                     # gates at 0 or 1, tanh at +-1, and a few pre-activations whose exp overflows to inf
-        xproj, whh = u(2, T, B, 4 * H) * 8, u(2, 4 * H, H) * 0.3
-        n = xproj.numel()
-        idx = torch.randint(0, n, (max(8, n // 500),), generator=g)
-        xproj.view(-1)[idx] = torch.where(torch.rand(idx.numel(), generator=g) < 0.5, -100.0, 100.0)
-    else:                                     # small cells: f ~ 0.0025, i ~ 1, g in +-0.2 - |c| straddles tanhf_'s switch at 0.1
-        xproj = torch.empty(2, T, B, 4, H)
-        xproj[:, :, :, 0] = 6 + u(2, T, B, H) * 0.5
-        xproj[:, :, :, 1] = -6 + u(2, T, B, H) * 0.5
-        xproj[:, :, :, 2] = u(2, T, B, H) * 0.2
-        xproj[:, :, :, 3] = u(2, T, B, H) * 0.5
-        xproj = xproj.reshape(2, T, B, 4 * H)
-        whh = u(2, 4 * H, H) * 0.02
-    for b in range(B):
-        xproj[:, lens[b]:, b] = 0.37              # junk past the lengths must not leak
-    dy = u(T, B, 2 * H)
-    mask = (torch.rand(T, B, 2 * H, generator=g) < 0.5).float() * 2.0
-    return xproj.contiguous(), whh.contiguous(), dy, mask
-
-
-_CACHE = {}
-
-
-def case(T, B, H, lens_kind, regime):
-    key = (T, B, H, lens_kind, regime)
-    if key not in _CACHE:
-        lens = [T] * B if lens_kind == "full" else _ragged(T, B)
-        seed = (T * 1000 + B) * 10000 + H + ("ref", "sat", "small").index(regime)
-        xproj, whh, dy, mask = make_inputs(T, B, H, lens, regime, seed)
-        refs = lr.Refs(xproj, whh, lens, dy, mask)
-        if regime == "small":
-            c = refs.f64[2].abs()[:, refs.valid]
-            frac = float(((c >= 0.05) & (c <= 0.15)).double().mean())
-            assert frac >= 0.10, "small-cell regime: only %.3f of the valid cells have |c| in [0.05, 0.15]" % frac
-        _CACHE[key] = (lens, xproj, whh, dy, mask, refs)
-    return _CACHE[key]
 
 
 def _run_child(code, args, env=None, timeout=300):

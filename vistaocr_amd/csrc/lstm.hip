@@ -2494,12 +2494,14 @@ static int lstm_bwd_impl(const float* dy, const float* dy_mask, const float* whh
     const float* whh_rev = whht_rev;
     VOCR_CHECK_ARG(dy && whh_fwd && whh_rev && lens && gates && cell && dgates && workspace, "vocr_lstm_bwd: null pointer");
     VOCR_CHECK_ARG(t > 0 && b > 0 && b <= 64 && h > 0 && h % 16 == 0, "vocr_lstm_bwd: need 1<=B<=64 and H%%16==0 (B=%d H=%d)", b, h);
+    // every backward kernel, the generic per-step one included, loads a unit's four gates as one f32x4
+    VOCR_CHECK_ARG(aligned16(gates), "vocr_lstm_bwd: gates must be 16-byte aligned");
     VOCR_CHECK_SWEEP_ENV(true);
     hipStream_t s = (hipStream_t)stream;
     float* dcb = (float*)workspace;
     const int rt = (b + 15) / 16;
     const bool fast = (h == 128 || h == 256 || h == 512) && aligned16(whh_fwd) && aligned16(whh_rev) && aligned16(dgates);
-    const SweepKind kind = lstm_sweep_kind(true, b, h, fast && 8 * (h / 16) <= resident_workgroup_capacity() && aligned16(gates));
+    const SweepKind kind = lstm_sweep_kind(true, b, h, fast && 8 * (h / 16) <= resident_workgroup_capacity());
     VOCR_CHECK_ARG(!packed_rows || kind == SWEEP_WIDE4 || kind == SWEEP_CHAIN4, "vocr_lstm_bwd_packed: no 4-row chain sweep for B=%d H=%d", b, h);
     if (kind != SWEEP_STEP) {
         // arrival flags: [chain <= 8][32 workgroups] at [0..255]; status words at [512..]
