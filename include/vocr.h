@@ -828,7 +828,8 @@ int vocr_ctc_entropy(const float* logits, const int32_t* lens, int t, int b, int
 
 /* ---- optimiser: grad clamp + torch.optim.Adam — src/train_cnn_lstm.py:143-149,363 -------------------------- */
 /* g = clamp(g*grad_scale, -clamp, clamp) (+ wd*p); Adam(m, v); step is the 1-based step count.  A NaN gradient stays NaN
- * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL). */
+ * (torch's clamp_ propagates NaN) and sets health[1] (health may be NULL).  clamp < 0 or NaN: VOCR_EINVAL, as vocr_clamp;
+ * count == 0: VOCR_OK, nothing touched. */
 int vocr_clamp_adam(float* p, const float* g, float* m, float* v, size_t count, float lr, float beta1, float beta2,
                     float eps, float weight_decay, float clamp, float grad_scale, int step, int32_t* health, void* stream);
 /* in place x = clamp(x, -clamp, clamp), NaN preserved: `param.grad.data.clamp_(min=-5, max=5)` (train_cnn_lstm.py:143-145)

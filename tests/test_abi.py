@@ -113,6 +113,13 @@ def test_argument_validation_without_gpu():
     assert lead(one, None, None, None, None, None) == -1 and b"next_wpack without next_planes" in lib.vocr_last_error()
     assert lib.vocr_lstm_fwd_lead(one, None, one, one, one, one, one, one, one, 8, 8, 512, 0, one, None, None, one, None, None) == -1
     assert lib.vocr_dropout_mask(one, 16, 1.0, 1, None) == -1 and lib.vocr_dropout_mask(None, 16, 0.5, 1, None) == -1
+    # the clamp bound of both optimiser entry points: negative or NaN is refused in front of any launch (one contract for the two)
+    adam = lambda clamp, count=16: lib.vocr_clamp_adam(one, one, one, one, count, 1e-3, 0.9, 0.999, 1e-8, 0.0, clamp, 1.0, 1, None, None)
+    assert adam(-1.0) == -1 and b"vocr_clamp_adam: clamp" in lib.vocr_last_error()
+    assert adam(float("nan")) == -1 and b"vocr_clamp_adam: clamp" in lib.vocr_last_error()
+    assert adam(-1.0, 0) == -1 and adam(5.0, 0) == 0                                 # count 0: OK, but only for arguments that are legal
+    assert lib.vocr_clamp(one, 16, -1.0, None, None) == -1 and lib.vocr_clamp(one, 16, float("nan"), None, None) == -1
+    assert lib.vocr_clamp_adam(one, one, one, one, 16, 1e-3, 0.9, 0.999, 1e-8, 0.0, 5.0, 1.0, 0, None, None) == -1   # step is 1-based
     assert lib.vocr_gather_rows_fill_grad_workspace_bytes(96) == 64 * 96 * 4
     assert lib.vocr_gather_rows_fill_grad(one, None, 4, 8, one, one, None) == -1
     assert lib.vocr_conv3x3_h16_plan(32, 64, 30, 600, 64) == 1 and lib.vocr_conv3x3_h16_plan(32, 24, 30, 600, 64) == 0

@@ -407,6 +407,7 @@ extern "C" int vocr_clamp_adam(float* p, const float* g, float* m, float* v, siz
                                float beta2, float eps, float weight_decay, float clamp, float grad_scale, int step,
                                int32_t* health, void* stream) {
     VOCR_CHECK_ARG(p && g && m && v && step >= 1, "vocr_clamp_adam: bad argument");
+    VOCR_CHECK_ARG(clamp >= 0.f, "vocr_clamp_adam: clamp must be >= 0 (got %g)", (double)clamp);   // false for NaN too, as in vocr_clamp
     if (count == 0) return VOCR_OK;
     // bias corrections in double on the host, exactly the scalars torch.optim.Adam derives per step
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
