@@ -159,7 +159,8 @@ int vocr_bn_train_stats(const float* y, int n, int c, int hw, float eps, float m
 /* eval: mean/invstd from running stats */
 int vocr_bn_eval_stats(const float* running_mean, const float* running_var, int c, float eps,
                        float* mean, float* invstd, void* stream);
-/* out = relu((y-mean)*invstd*gamma + beta) */
+/* out = relu((y-mean)*invstd*gamma + beta), the ReLU as `v > 0 ? v : 0`: a NaN pre-activation (a NaN in y or in a statistic) comes out
+ * as 0, where torch's relu would keep the NaN.  The same holds for every fused forward below that contains this pass. */
 int vocr_bn_relu_apply(const float* y, const float* mean, const float* invstd, const float* gamma,
                        const float* beta, float* out, int n, int c, int hw, void* stream);
 /* Training-mode BatchNorm2d + ReLU of a layer in TWO launches instead of three (round 4): the statistics pass leaves per-chunk
@@ -170,7 +171,9 @@ int vocr_bn_relu_apply(const float* y, const float* mean, const float* invstd, c
 int vocr_bn_train_relu_apply(const float* y, const float* gamma, const float* beta, float* out, int n, int c, int hw, float eps,
                              float momentum, float* mean, float* invstd, float* running_mean, float* running_var,
                              int64_t* num_batches_tracked, float* xhat_sum, void* workspace, void* stream);
-/* The same for a layer followed by FractionalMaxPool2d (vocr_bn_relu_fracpool2x2_fwd's pass, src/models/cnnlstm.py:127,130). */
+/* The same for a layer followed by FractionalMaxPool2d (vocr_bn_relu_fracpool2x2_fwd's pass, src/models/cnnlstm.py:127,130):
+ * bit-identical to vocr_bn_train_stats followed by vocr_bn_relu_fracpool2x2_fwd.  A NaN or an infinity in y makes its channel's
+ * statistics non-finite; every activation of that channel is then 0 (see vocr_bn_relu_apply) and every window elects its first pixel. */
 int vocr_bn_train_relu_fracpool2x2_fwd(const float* y, const float* gamma, const float* beta, const float* samples, float* out,
                                        int32_t* idx, int n, int c, int h, int w, int oh, int ow, float eps, float momentum,
                                        float* mean, float* invstd, float* running_mean, float* running_var,
@@ -183,18 +186,23 @@ int vocr_bn_relu_bwd(const float* da, const float* y, const float* mean, const f
                      float* dconv_bias, int n, int c, int hw, void* workspace, void* stream);
 
 /* ---- FractionalMaxPool2d(2, output_ratio=(0.5,0.7)) — src/models/cnnlstm.py:127,130 --------------------- */
-/* samples[n][c][2] (u_w, u_h) as ATen's _random_samples; idx = flat h*W+w of the winner (int32) */
+/* samples[n][c][2] (u_w, u_h) as ATen's _random_samples; idx = flat h*W+w of the winner (int32).  1 <= oh <= h-1, 1 <= ow <= w-1
+ * (out 1: the one window sits at in-2).  Bit for bit ATen's CPU op, non-finite inputs included (`val > max || isnan(val)`): a NaN
+ * takes every window it lies in (the last NaN of several) and a window of four -inf keeps its first pixel. */
 int vocr_fracpool2x2_fwd(const float* x, const float* samples, float* out, int32_t* idx,
                          int n, int c, int h, int w, int oh, int ow, void* stream);
 /* BatchNorm-apply + ReLU + the same pooling in one pass over the conv output y (vocr_bn_relu_apply followed by
- * vocr_fracpool2x2_fwd, bit for bit), for layers whose activation is only ever consumed by the pool. */
+ * vocr_fracpool2x2_fwd, bit for bit), for layers whose activation is only ever consumed by the pool.  The pooled activation is
+ * never NaN or negative: a NaN or -inf in y is 0 before the pool sees it (vocr_bn_relu_apply). */
 int vocr_bn_relu_fracpool2x2_fwd(const float* y, const float* mean, const float* invstd, const float* gamma,
                                  const float* beta, const float* samples, float* out, int32_t* idx,
                                  int n, int c, int h, int w, int oh, int ow, void* stream);
 /* Backward of vocr_bn_relu_fracpool2x2_fwd in one go: dout/idx are the pooled gradient and winner indices, samples the
  * forward's; returns dy = dL/d(conv output), dgamma, dbeta, dconv_bias like vocr_bn_relu_bwd, without materialising the
  * un-pooled gradient.  Needs window starts that strictly increase (vocr_bn_relu_fracpool2x2_bwd_supported: both
- * (in-2)/(out-1) >= 1.01, true for the reference's 0.5 x 0.7 ratios); otherwise use vocr_fracpool2x2_bwd + vocr_bn_relu_bwd. */
+ * (in-2)/(out-1) >= 1.01 in float32, true for the reference's 0.5 x 0.7 ratios; w % 4 == 0; (2w + 8 + 2h) * 4 <= 65536 bytes of
+ * LDS for the inverse window maps, met with equality at h = 4, w = 8184); otherwise use vocr_fracpool2x2_bwd + vocr_bn_relu_bwd.
+ * A refused shape returns an error before anything is launched.  y and dy are read and written as 16-byte pixel groups. */
 int vocr_bn_relu_fracpool2x2_bwd_supported(int h, int w, int oh, int ow);
 int vocr_bn_relu_fracpool2x2_bwd(const float* dout, const int32_t* idx, const float* samples, const float* y,
                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -206,6 +214,10 @@ int vocr_fracpool2x2_bwd(const float* dout, const int32_t* idx, float* dx,
                          int n, int c, int h, int w, int oh, int ow, void* stream);
 
 /* ---- rapid_ds tail: ReLU + MaxPool2d(2,2) — src/models/cnnlstm.py:119-120 -------------------------------- */
+/* out[n][c][h/2][w/2] = max over the 2x2 window of max(x, 0) (fmaxf: a NaN in x counts as 0, where torch propagates it), idx = flat
+ * h*W+w of the first maximum; an odd last row / column is dropped.
+ * The backward stores dout where out > 0 (else 0) at each winner and touches nothing else: dx must arrive ZERO-FILLED - the three
+ * pixels of a window that did not win, and the dropped odd row / column, keep what the caller put there. */
 int vocr_relu_maxpool2_fwd(const float* x, float* out, int32_t* idx, int n, int c, int h, int w, void* stream);
 int vocr_relu_maxpool2_bwd(const float* dout, const float* out, const int32_t* idx, float* dx,
                            int n, int c, int h, int w, void* stream);

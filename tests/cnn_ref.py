@@ -208,11 +208,16 @@ def bn_bwd_bars(da, y, mask, mean, invstd, gamma, dgamma, dbeta, e_xhat):
     return b_dy, b_dgamma, b_dbeta
 
 
+def xhat_sum_bound(mean, invstd, count):
+    """the bound on |xhat_sum| that conv_bias_grad_bar is built from"""
+    return count * (U * mean.abs() + SUM_DEPTH * EPS64 * mean.abs()) * invstd + SUM_DEPTH * EPS64 * count ** 0.5
+
+
 def conv_bias_grad_bar(mean, invstd, gamma, dgamma, count):
     """The conv-bias gradient of a batch-statistics BatchNorm is 0 in exact arithmetic; the kernels return -gamma invstd (dgamma / count)
     xhat_sum, where xhat_sum = count (mean - m32) invstd is the rounding residue of the fp32 mean (|mean - m32| <= U |mean|, + the
     double sum's own error).  The bar is that bound, twice over."""
-    xs = count * (U * mean.abs() + SUM_DEPTH * EPS64 * mean.abs()) * invstd + SUM_DEPTH * EPS64 * count ** 0.5
+    xs = xhat_sum_bound(mean, invstd, count)
     return 2 * (_f(gamma).abs() * invstd * dgamma.abs() / count * xs) + 4 * U * dgamma.abs() / count + 1e-30
 
 
@@ -235,7 +240,8 @@ def fracpool_starts(u, in_size, out_size, arith=np.float32):
 
 def fracpool2x2(x, samples, oh, ow, arith=np.float32):
     """FractionalMaxPool2d(2) with explicit samples [n][c][2] = (u_w, u_h): (out, idx = flat h * W + w of the first maximum in
-    row-major window order), computed on x's device."""
+    row-major window order), computed on x's device.  ATen's rule, `val > max || isnan(val)`: a NaN takes the window (the last one of
+    several), index included; a window of four -inf keeps its first pixel."""
     n, c, h, w = x.shape
     s = samples.detach().cpu().numpy()
     sw = torch.tensor(np.stack([[fracpool_starts(s[i, j, 0], w, ow, arith) for j in range(c)] for i in range(n)]), device=x.device)
@@ -249,7 +255,7 @@ def fracpool2x2(x, samples, oh, ow, arith=np.float32):
             if best is None:
                 best, bidx = v, ii
             else:
-                take = v > best                      # the first maximum wins
+                take = (v > best) | torch.isnan(v)   # the first maximum wins; a NaN always does
                 best, bidx = torch.where(take, v, best), torch.where(take, ii, bidx)
     return best, bidx
 

@@ -281,7 +281,8 @@ def test_conv_bn_relu_fn(dev, n, c, h, w):
 def test_conv_bn_relu_pool_fused_backward(dev, n, c, h, w):
     """Conv -> BatchNorm -> ReLU -> FractionalMaxPool2d as ONE layer op (pool fused into the BN pass forward; pooling gradient,
     ReLU and BatchNorm backward fused into one pass backward) against the same chain on PyTorch-CPU with the same pool samples;
-    samples include 0 and the largest float32 below 1 (the last two windows then coincide in float32 interval arithmetic)."""
+    samples include 0 and the largest float32 below 1 (the last two windows along w then OVERLAP by one column in float32 interval
+    arithmetic - start in - 3 beside the pinned in - 2; they never coincide: tests/test_bnpool_cases_cpu.py)."""
     import os
     from vistaocr_amd import ops
     cin = 8
