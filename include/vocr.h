@@ -41,10 +41,11 @@ const char* vocr_last_error(void);
  * cleared by the caller, LSTM workspace survives between the vocr_lstm_fwd_range calls of a sweep, larger vocr_gemm_workspace_bytes,
  * vocr_gemm_pair / vocr_lstm_bwd_parts / vocr_profile_range_*, x-fastest conv weight pack); 4 = round 5 (packed sequence rows:
  * vocr_lstm_*_packed, vocr_seq_rowmap, vocr_gather_rows; VOCR_LSTM_SWEEP validated; experiment switches compiled out); 5 = round 6
- * (the next layer's x-projection behind the forward sweep: vocr_lstm_fwd_lead / vocr_lstm_xproj_pack,
- * vocr_dropout_mask).  A binding compares vocr_abi_version()
+ * (vocr_dropout_mask, and the next layer's x-projection behind the forward sweep); 6 = that x-projection path removed again, slower
+ * than the GEMM in every form it was built in: four entry points for the follower waves, their weight pack, its size and their shape
+ * query are gone, and a forward sweep reads one x-projection.  A binding compares vocr_abi_version()
  * with the VOCR_ABI_VERSION it was written against and refuses a library that answers anything else. */
-#define VOCR_ABI_VERSION 5
+#define VOCR_ABI_VERSION 6
 int  vocr_abi_version(void);
 /* Named ranges on the profiler's timeline (rocprofv3 --marker-trace), nested push / pop on the calling thread.  roctx is dlopen'ed on
  * first use; returns 0 when the range was recorded, 1 when roctx is not available (not an error), negative on a bad argument.  The
@@ -276,7 +277,7 @@ int vocr_scale_dev(const float* x, const float* scalar, float* out, size_t count
 /* mask[i] = (hash(seed,i) >= p) ? 1/(1-p) : 0 ; out = x*mask */
 int vocr_dropout_fwd(const float* x, float* out, float* mask, size_t count, float p, uint64_t seed, void* stream);
 /* the mask of vocr_dropout_fwd alone (it depends on the seed and the element index only): lets a consumer that applies the mask itself
- * (vocr_lstm_xproj_follow) have it before x exists */
+ * (through vocr_mul, on packed rows) have it before x exists */
 int vocr_dropout_mask(float* mask, size_t count, float p, uint64_t seed, void* stream);
 
 /* ---- nn.LSTM recurrence on a packed, length-sorted batch — src/models/cnnlstm.py:148-149,288-290 ---------- */
@@ -428,29 +429,6 @@ int vocr_lstm_fwd_packed(const float* xproj, const float* whh_fwd, const float* 
 int vocr_lstm_bwd_packed(const float* dy, const float* dy_mask, const float* whht_fwd, const float* whht_rev, const int32_t* lens,
                          const float* gates, const float* cell, float* dgates, float* dbias, void* workspace, int t, int b, int h,
                          int rows, int32_t* health, void* stream);
-
-/* ---- the next layer's x-projection BEHIND the forward sweep — src/models/cnnlstm.py:148-149,288-290 (cuDNN's multi-layer RNN ---------
- * overlaps layer l+1's input GEMM with layer l's recurrence; nn.LSTM's inter-layer dropout: src/train_cnn_lstm.py:331) */
-/* A forward sweep is latency-bound and leaves most of every CU's matrix pipe idle.  vocr_lstm_fwd_lead is vocr_lstm_fwd (rows = 0) /
- * vocr_lstm_fwd_packed (rows > 0) with two additions:
- *  - xproj2 (may be NULL): a second addend of this layer's x-projection, same layout as xproj ([2][rows][4H]); the sweep reads
- *    xproj + xproj2.
- *  - next_wpack != NULL: four more waves in every workgroup of the sweep compute the NEXT layer's x-projection from the rows the sweep
- *    has produced so far (16 steps of a chain at a time, throttled by the chain so that they use the matrix pipe while it waits for its
- *    hand-off): the chain's OWN direction half of y (x y_mask, the pre-scaled inter-layer dropout mask [rows][2H], or NULL), K = H, by
- *    the matching half of W_ih of both directions of the next layer, so neither direction waits for the other:
- *        next_planes[src][tgt][row][4H] = y[row][src*H .. src*H+H) . W_ih(next, tgt)[:, src*H .. src*H+H)^T  (+ next_bias[tgt][4H] in src = 0)
- *    and the next layer's vocr_lstm_fwd_lead takes xproj = next_planes (planes [0][.]), xproj2 = next_planes + 2*rows*4H.
- *    next_wpack: W_ih of the next layer, both directions, in MFMA-fragment order: vocr_lstm_xproj_pack_bytes(h) bytes written by
- *    vocr_lstm_xproj_pack whenever the weights change; next_bias [2][4H] may be NULL.
- * Shapes: vocr_lstm_follow_supported (16 < B <= 32, H = 512 = the next layer's H, the wide 4-row chain sweep); rows < 262144. */
-int vocr_lstm_follow_supported(int b, int h);
-size_t vocr_lstm_xproj_pack_bytes(int h);
-int vocr_lstm_xproj_pack(const float* w_ih_fwd, const float* w_ih_rev, float* wpack, int h, void* stream);
-int vocr_lstm_fwd_lead(const float* xproj, const float* xproj2, const float* whh_fwd, const float* whh_rev, const int32_t* lens,
-                       float* y, float* gates, float* cell, void* workspace, int t, int b, int h, int rows,
-                       const float* next_wpack, const float* next_bias, const float* y_mask, float* next_planes,
-                       int32_t* health, void* stream);
 
 /* ---- CTC: warpctc_pytorch.CTCLoss — src/train_cnn_lstm.py:358,138 ------------------------------------------ */
 /* logits[T][B][V] pre-softmax, blank = 0.  labels flat int32 (device), label_offsets[B], label_lens[B],

@@ -6,7 +6,6 @@ bash scripts/_trace_config.sh c5 $T > $D/${T}_c5.log 2>&1
 python scripts/lstm_ab.py "" "T=576" > $D/$T/lstm_sweeps_alone.txt 2>&1
 python scripts/gemm_bench.py > $D/$T/gemm_bench.txt 2>&1
 python scripts/x6_bench.py > $D/$T/x6_bench.txt 2>&1
-python scripts/follow_ab.py > $D/$T/follow_ab.txt 2>&1
 hipcc --offload-arch=gfx950 -O3 -w -o /tmp/mfma_rate scripts/mfma_rate.hip && /tmp/mfma_rate > $D/$T/mfma_rate.txt 2>&1
 tail -3 $D/${T}_prof.log | cut -c1-600; tail -4 $D/$T/x6_bench.txt; cat $D/$T/mfma_rate.txt | head -4
 # the opt-in fp16x3 split: its products alone, and the step under both splits on this box

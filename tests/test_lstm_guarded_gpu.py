@@ -1,7 +1,6 @@
 """GPU: every LSTM entry point the product runs, called on the C entry (_lib.call) in memory the test owns to the byte (tests/guarded.py):
 vocr_lstm_fwd, vocr_lstm_fwd_range, vocr_lstm_bwd, vocr_lstm_bwd_bias, vocr_lstm_bwd_parts + vocr_lstm_bias_from_parts,
-vocr_lstm_fwd_packed, vocr_lstm_bwd_packed, vocr_seq_rowmap, vocr_gather_rows, vocr_gather_rows_fill_grad.  (vocr_lstm_fwd_lead and
-vocr_lstm_xproj_pack: tests/test_lead_gpu.py.)
+vocr_lstm_fwd_packed, vocr_lstm_bwd_packed, vocr_seq_rowmap, vocr_gather_rows, vocr_gather_rows_fill_grad.
 
 The library reads VOCR_LSTM_SWEEP / VOCR_LSTM_WRITE_THROUGH once per process and persistent sweeps must not share the device, so every
 setting is ONE child process (this module, child_main), one after the other, each under a time limit sized to its work; one more child

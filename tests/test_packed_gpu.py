@@ -5,12 +5,18 @@ tests/test_configs_gpu.py run packed by default and hold the packed path to the 
   * vocr_gather_rows: packing and unpacking with and without a fill row;
   * one BiLSTM layer, packed vs dense, on the 4-row sweeps of every shape class (wide members, 4-wave members at B <= 16 and at H = 256,
     a partial last chain): y / dx on every real frame and all weight gradients;
-  * the whole model on a ragged batch: logits (padded frames = the output layer's bias, bit for bit), loss, greedy labels, every gradient."""
+  * the whole model on a ragged batch: logits (padded frames = the output layer's bias, bit for bit), loss, greedy labels, every gradient;
+  * GatherRowsFn's fill gradient (the bias of the output layer under a loss that is not zero on padded frames)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -215,3 +221,47 @@ def test_packed_sweep_refuses_a_row_count_that_does_not_fit_the_lengths(dev):
          ws.data_ptr(), T, B, H, rows, hw.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert int(hw[0]) == 0
+
+
+_MODEL_CODE = r'''
+import sys, torch
+sys.path.insert(0, %(root)r)
+import vistaocr_amd as va
+from vistaocr_amd import ops
+torch.manual_seed(3)
+B, Hh, W = %(B)d, 30, %(W)d
+m = va.CnnOcrModel(num_in_channels=1, input_line_height=Hh, rds_line_height=Hh, lstm_input_dim=128, num_lstm_layers=3, num_lstm_hidden_units=512,
+                   p_lstm_dropout=0.5, alphabet=va.english_alphabet(), multigpu=False, verbose=False, gpu=True)
+m.train()
+g = torch.Generator().manual_seed(11)
+x = torch.rand(B, 1, Hh, W, generator=g)
+widths = torch.tensor(sorted([int(W - (%(ragged)d * i * W) // (2 * B)) for i in range(B)], reverse=True))
+m.pool_samples = [torch.rand(B, 64, 2, generator=g), torch.rand(B, 128, 2, generator=g)]
+m.pack_threshold = %(thr)f
+logits, lens = m(x.cuda(), widths)
+T = logits.shape[0]
+wgt = torch.rand(logits.shape, generator=g).cuda()
+loss = (logits * wgt).sum() + (logits ** 2).sum() * 0.01          # NOT zero on padded frames: the fill row's gradient is live
+loss.backward()
+ops.check_health_sync(torch.device("cuda:0"))
+torch.save({"logits": logits.detach().cpu(), "lens": lens, "grads": {k: p.grad.detach().cpu() for k, p in m.named_parameters()}}, sys.argv[1])
+'''
+
+
+def test_fill_row_gradient_of_the_packed_path(dev, tmp_path):
+    """The output layer's bias gradient under a loss that is not zero on padded frames: packed rows (the bias row fills the frames
+    without a packed row: GatherRowsFn returns their column sum) against the dense path."""
+    outs = []
+    for thr in (0.0, 0.95):
+        f = str(tmp_path / ("p%d.pt" % int(thr * 100)))
+        code = _MODEL_CODE % dict(root=ROOT, B=12, W=200, ragged=1, thr=thr)
+        r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-1500:]
+        outs.append(torch.load(f))
+    a, b = outs
+    k = [n for n in a["grads"] if n.startswith("prob_layer") and n.endswith("bias")][0]
+    ga, gb = a["grads"][k], b["grads"][k]
+    assert (ga - gb).abs().max().item() <= 1e-4 * max(1.0, ga.abs().max().item()), (ga - gb).abs().max().item()
+    for n in a["grads"]:
+        tol = 3e-4 * max(1e-3, a["grads"][n].abs().max().item())
+        assert (a["grads"][n] - b["grads"][n]).abs().max().item() <= tol, n

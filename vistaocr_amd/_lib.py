@@ -99,10 +99,6 @@ SIGNATURES = {
     "vocr_gather_rows_fill_grad_workspace_bytes": (Z, [I]),
     "vocr_gather_rows_fill_grad": (I, [P, P, ctypes.c_long, I, P, P, P]),
     "vocr_lstm_fwd_packed": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
-    "vocr_lstm_follow_supported": (I, [I, I]),
-    "vocr_lstm_xproj_pack_bytes": (Z, [I]),
-    "vocr_lstm_xproj_pack": (I, [P, P, P, I, P]),
-    "vocr_lstm_fwd_lead": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
     "vocr_lstm_bwd_packed": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P]),
     "vocr_ctc_workspace_bytes": (Z, [I, I, I, I]),
     "vocr_ctc_loss_grad": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
@@ -141,7 +137,7 @@ SIGNATURES = {
     "vocr_comm_destroy": (I, [P]),
 }
 
-ABI_VERSION = 5          # include/vocr.h: VOCR_ABI_VERSION
+ABI_VERSION = 6          # include/vocr.h: VOCR_ABI_VERSION
 
 _lib = None
 

@@ -818,32 +818,9 @@ __global__ __launch_bounds__(256) void lstm_fwd_chain4v(const float* __restrict_
 #endif
 }
 
-// The next layer's x-projection, computed WHILE this layer's forward sweep runs (cuDNN's RNN overlaps the two:
-// src/models/cnnlstm.py:148-149,288-290).  A sweep is latency-bound: its 4x4x1 MFMAs keep a CU's matrix pipe ~42 % busy.  Four MORE
-// waves of the sweep's own workgroup (waves 8 - 11 of lstm_fwd_chain4w<8, true>: one per SIMD, 168 registers each like the chain's)
-// multiply the rows the chain has already produced:
-//   unit = 16 consecutive steps of the chain = 64 rows x K = H (the chain's OWN direction half of y: a direction's rows appear in its
-//   own time order, so neither direction waits for the other) x this member's 256 of the next layer's 8H gate columns (both
-//   directions); out[src dir][tgt dir][row][4H'] - the next sweep adds the two source planes (xproj2);
-//   A = the 64 x 512 panel (x the inter-layer dropout mask, if any) staged once per unit into LDS as MFMA fragments
-//   [16-byte piece kq][row ^ 8 (kq & 1)] (conflict-free 16-byte writes and reads); B = vocr_lstm_xproj_pack's fragment order, one
-//   contiguous KB per (32 columns, 8 k) straight from L2 into registers, three chunks in flight; v_mfma_f32_32x32x2_f32, wave tile
-//   64 x 64 in 64 AGPRs.
-// Why inside the workgroup (all measured, scripts/follow_ab.py, HISTORY of round 6 in DESIGN.md): as a kernel of its own beside the
-// sweep (a) a never-stalling MFMA stream takes the matrix pipe from the chain whatever its instruction length, stream priority or
-// s_setprio - the sweep ran at HALF speed -, (b) its workgroups land on other XCDs than their chain (the dispatcher's round robin
-// continues where the previous kernel stopped) and sc1 stores are not seen there before the producer's final L2 write-back, (c) placed
-// first it can keep the sweep's workgroups off the CU.  Here the throttle is explicit: the chain's wave 0 raises `phase` (LDS) when its
-// MFMAs of a step begin; at the next yield point (after every 16 MFMAs = 1024 cycles of the pipe, in every wait loop) a follower wave
-// goes to the step's two barriers and sits there through the chain's MFMAs, reduction and activation - its window is the chain's
-// cell update + hand-off round trip, ~half of a step - and it arrives at the first barrier long before the chain does.
-// Gates: rows of chain steps <= joined - 3 are complete when this workgroup has passed `joined` first-barriers (every wave has then
-// seen its slice of h of step joined - 2, and a member's cell waves drain their own y stores before they store the next h); the
-// chain's last rows: the 32 `done` words (one per cell wave) of all 16 members, stored behind a release.  A chain spread over several
-// XCDs (never seen; the hand-off then runs write-through) only trusts the `done` words: its projection runs as a tail.
-// Sync among the four follower waves (panel staged / panel consumed): LDS counters, never s_barrier.
-// Stores through a wave-uniform 64-bit base (SGPR pair) + a 32-bit per-thread byte offset: the compiler keeps a 64-bit VGPR address per
-// stream instead (10 VGPRs in lstm_fwd_chain4w's cell section, which has none to spare beside the follower waves)
+// Stores of lstm_fwd_chain4w's cell section (hand-off ring, y, gates, cell): a wave-uniform 64-bit base (SGPR pair) + a 32-bit
+// per-thread byte offset that never changes.  Written as plain pointer stores the compiler keeps a 64-bit VGPR address per stream
+// instead: 10 VGPRs in a kernel that holds 128 of W_hh per lane and sits at 170.
 __device__ __forceinline__ void sstore_b32(const void* sbase, unsigned voff, float v) {
     asm volatile("global_store_dword %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
 }
@@ -857,185 +834,6 @@ __device__ __forceinline__ void sstore_b128(const void* sbase, unsigned voff, f3
     asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
 }
 
-constexpr unsigned kFollowDone = 0xFFFFFFFCu;      // a member's `done` word (0xFF fill) once both its cell waves have cleared their bit
-struct FollowArgs {
-    const float* wpack;      // next layer's W_ih, vocr_lstm_xproj_pack order; nullptr: nobody follows
-    const float* mask;       // [rows][2H] pre-scaled dropout mask or nullptr
-    const float* bias;       // [2][4H'] or nullptr
-    float* out;              // [2 src][2 tgt][rows][4H']
-    unsigned* done;          // the sweep's id block: word [chain*32 + 16 + member] (the upper half of a chain's 32 id words is free)
-    unsigned long long* dbg; // -DVOCR_FOLLOW_PROBE builds: stamps (the workspace's first words, unused by a forward sweep)
-    int mode;                // -DVOCR_FOLLOW_PROBE builds: parts of the follower switched off (WRONG results)
-};
-
-template <bool MASK, typename Yield>
-__device__ __forceinline__ void xproj_follow_waves(const FollowArgs& fa, const float* y, float* panel, int* fsync, const SeqRows& sr, int dir, int nrows,
-                                                   int chain, int slice, bool local, const int& joined, Yield&& yield, unsigned* status, unsigned* health) {
-    constexpr int H = 512, G = 4 * H, TG = 16, NJ = H / 8;
-    const int tid = threadIdx.x - 512, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int Tc = sr.steps;
-    const long R = sr.total;
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, (int)(R * 2 * H * 4), 0x00020000);
-    // staging: lane = (row_lo = lane & 7, kq_lo = lane >> 3): 8 rows x 128 contiguous bytes per instruction
-    const int srow_lo = lane & 7, skq_lo = lane >> 3;
-    // B fragments of this wave's two 32-column tiles: scalar offset = (tile, chunk), vector offset = lane
-    const int col0 = slice * 256 + wave * 64;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)fa.wpack, 0, 2 * 8 * H * H * 4, 0x00020000);
-    const int wbase = ((dir * (8 * H / 32) + col0 / 32) * NJ) * 1024;        // bytes; tile ct: + NJ KB, chunk j: + 1 KB
-    auto b_load = [&](int ct, int j) {
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, wbase + (ct * NJ + j) * 1024, 0);
-        return (f32x4){__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-    };
-    // the member's 256 columns lie in ONE of the four [src dir][tgt dir] planes
-    const int tgt = col0 / G;
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(fa.out + (long)(dir * 2 + tgt) * R * G), 0, (int)(R * G * 4), 0x00020000);
-    const int li = lane & 31, lk = lane >> 5;
-    float bv[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) bv[ct] = (dir == 0 && fa.bias) ? fa.bias[col0 + 32 * ct + li] : 0.f;
-    int* fstaged = fsync;            // + 1 per wave and unit when its quarter of the panel is in LDS
-    int* fconsumed = fsync + 1;      // + 1 per wave and unit when it has read the panel for the last time
-    bool failed = false;
-    const int units = (Tc + TG - 1) / TG;
-    for (int u = 0; u < units; ++u) {
-        const int s_lo = u * TG, s_hi = min(s_lo + TG, Tc);
-#ifdef VOCR_FOLLOW_PROBE
-        if (tid == 0 && slice == 0 && chain < 2 && u < 24) fa.dbg[chain * 64 + u] = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0 && slice == 0 && chain < 2 && u < 24) fa.dbg[chain * 64 + 32 + u] = joined;
-#endif
-        // ---- gate: rows of steps < s_hi are complete, and every wave is done with the previous unit's panel
-        {
-            const bool by_done = !local || s_hi + 2 > Tc;                   // joined never exceeds Tc
-            unsigned spins = 0;
-            for (;;) {
-                yield();
-                bool ok;
-                if (by_done) {
-                    unsigned v = kFollowDone;
-                    if (lane < 16) v = __hip_atomic_load(fa.done + chain * 32 + 16 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = __all(v == kFollowDone);
-                    if (ok) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                } else {
-                    ok = joined >= s_hi + 2;
-                }
-                if (ok && __hip_atomic_load(fconsumed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= 4 * u) break;
-                if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u || ++spins > (1u << 24)) { failed = true; break; }
-                if (by_done) __builtin_amdgcn_s_sleep(8); else __builtin_amdgcn_s_sleep(2);
-                if (by_done && !ok) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-        }
-#ifdef VOCR_FOLLOW_PROBE
-        const int pmode = fa.mode;
-#else
-        constexpr int pmode = 0;
-#endif
-        // ---- stage this wave's quarter of the 64 x 512 panel
-        if (!failed && pmode != 2) {
-#pragma unroll 1
-            for (int i = 0; i < 32; i += 4) {
-                u32x4_t v[4];
-                f32x4 mk[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c = (i + q) * 4 + wave, row = (c & 7) * 8 + srow_lo, kq = (c >> 3) * 8 + skq_lo;
-                    const int s = s_lo + (row >> 2), r = row & 3;
-                    const bool ok = s < s_hi && r < nrows;
-                    const int t = dir == 0 ? s : Tc - 1 - s;
-                    const long grow = sr.base + (long)sr.stride * t + r;
-                    // rows past the chain's end / the batch: an out-of-range offset reads as zeros
-                    v[q] = __builtin_amdgcn_raw_buffer_load_b128(yrsrc, ok ? (int)((grow * 2 * H + dir * H + 4 * kq) * 4) : -16, 0, kPollAux);
-                    if (MASK) mk[q] = *(const f32x4*)(fa.mask + (ok ? grow * 2 * H + dir * H + 4 * kq : 0));
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c = (i + q) * 4 + wave, row = (c & 7) * 8 + srow_lo, kq = (c >> 3) * 8 + skq_lo;
-                    f32x4 a = (f32x4){__uint_as_float(v[q][0]), __uint_as_float(v[q][1]), __uint_as_float(v[q][2]), __uint_as_float(v[q][3])};
-                    if (MASK) a = a * mk[q];
-                    *(f32x4*)(panel + ((long)kq * 64 + (row ^ ((kq & 1) << 3))) * 4) = a;
-                }
-                yield();
-            }
-        }
-        if (lane == 0) __hip_atomic_fetch_add(fstaged, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        {
-            unsigned spins = 0;
-            while (__hip_atomic_load(fstaged, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 4 * (u + 1)) {
-                yield();
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 24)) { failed = true; break; }
-            }
-        }
-        // ---- 64 x 64 wave tile over K = 512
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-        if (!failed && pmode != 1 && pmode != 2) {
-            constexpr int D = 4;                              // B chunks in flight
-            f32x4 bq[D][2];
-#pragma unroll
-            for (int d = 0; d < D; ++d)
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) bq[d][ct] = b_load(ct, d);
-            const float* ap = panel + ((long)lk * 64 + (li ^ (lk << 3))) * 4;       // piece kq = 2j + lk, row tile rt: + 32 rows
-            f32x4 af[2][2];                                   // [parity of the chunk][row tile]: one chunk ahead
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) af[0][rt] = *(const f32x4*)(ap + 32 * rt * 4);
-#pragma unroll 1
-            for (int j0 = 0; j0 < NJ; j0 += D) {
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    const int j = j0 + d, jn = min(j + 1, NJ - 1), jl = min(j + D, NJ - 1);      // clamped: the last loads repeat, nothing branches
-#pragma unroll
-                    for (int rt = 0; rt < 2; ++rt) af[(d + 1) & 1][rt] = *(const f32x4*)(ap + ((long)(2 * jn) * 64 + 32 * rt) * 4);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                            for (int ct = 0; ct < 2; ++ct)
-                                acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[d & 1][rt][e], bq[d][ct][e], acc[rt][ct], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    // the slot just consumed takes chunk j + D: D - 1 chunks (3 x 1024 MFMA cycles) of flight
-                    if (pmode != 3) {
-#pragma unroll
-                        for (int ct = 0; ct < 2; ++ct) bq[d][ct] = b_load(ct, jl);
-                    }
-                    if (pmode == 4) __builtin_amdgcn_s_sleep(8);
-                    if (pmode == 5) __builtin_amdgcn_s_sleep(16);
-                    yield();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        if (lane == 0) __hip_atomic_fetch_add(fconsumed, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        // ---- plane[row][4H]: C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                const int s = s_lo + (row >> 2), rr = row & 3;
-                const int t = dir == 0 ? s : Tc - 1 - s;
-                const long grow = sr.base + (long)sr.stride * t + rr;
-                const int off = (s < s_hi && rr < nrows) ? (int)((grow * G + col0 % G + li) * 4) : -4;      // out of range: dropped
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(failed ? __uint_as_float(0x7FC00000u) : acc[rt][ct][r] + bv[ct]), orsrc, off, 32 * ct * 4, 0);
-            }
-            yield();
-        }
-    }
-#ifdef VOCR_FOLLOW_PROBE
-    if (tid == 0 && slice == 0 && chain < 2) fa.dbg[chain * 64 + 30] = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (failed && lane == 0) raise_timeout(status, health);
-}
-
 // Forward sweep for 16 < B <= 32 at H = 512 ("chain4w": 4-row chains with WIDE members): 16 chains of 16 members with 32
 // units (128 gate columns) each = ONE 8-wave workgroup per CU.  Same FLOPs per CU and step as two lstm_fwd_chain4v workgroups,
 // but nothing shares the CU: a chain no longer moves at the pace of its most-disturbed member (with two workgroups per CU the
@@ -1044,13 +842,13 @@ __device__ __forceinline__ void xproj_follow_waves(const FollowArgs& fa, const f
 // gate column of a 64-column block, two blocks: 128 VGPRs of W_hh per lane, no duplicates; A straight from the hand-off load (one
 // 16-byte load per lane and step) through the instruction's A broadcast.  Epilogue: wave w reduces and activates gate w & 3 of
 // rows 2(w >> 2), +1 (a wave-uniform activation function), waves 0-1 update the 128 cells.  Ring and reset: lstm_fwd_chain4v.
-template <int KQ4, bool FOLLOW>
-__global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const float* __restrict__ xproj, const float* __restrict__ whh_f,
+template <int KQ4>
+__global__ __launch_bounds__(512) void lstm_fwd_chain4w(const float* __restrict__ xproj, const float* __restrict__ whh_f,
                                                         const float* __restrict__ whh_r, const int32_t* __restrict__ lens,
                                                         float* y, float* __restrict__ gates, float* __restrict__ cell,
                                                         float* hx, unsigned* ids, unsigned* status, unsigned* health, int T, int B, int NT4,
                                                         int force_wt, int s0, int s1, int nap, int packed_rows,
-                                                        const float* __restrict__ xproj2, FollowArgs fa) {
+                                                        const float* __restrict__ xproj2) {
     constexpr int H = 64 * KQ4;
     constexpr int members = H >> 5;                   // 32 units each
     constexpr int KW = H / 8;                         // k per wave
@@ -1061,10 +859,6 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
     float (*red)[4][RP] = (float (*)[4][RP])lds;                            // [wave][row][column]
     float (*actb)[128] = (float (*)[128])(lds + 8 * 4 * RP + 4);            // [row][gate*32 + unit]
     __shared__ int sig[2];                                                  // step count of the two cell waves' last h store
-    __shared__ int phase;                                                   // FOLLOW: steps whose MFMAs wave 0 has begun (the followers' cue)
-    __shared__ int fsync[2];                                                // FOLLOW: panel staged / consumed counters of the four follower waves
-    extern __shared__ __attribute__((aligned(16))) float panel[];           // FOLLOW: 128 KB, dynamic (a static array of that size makes the
-                                                                            // compiler assume one wave per SIMD and pad the register allocation)
     const int nch = 2 * NT4;
     const int chain = (int)(blockIdx.x & 7) + 8 * (int)((blockIdx.x >> 3) & 1), member = blockIdx.x >> 4;
     if (chain >= nch) return;
@@ -1074,32 +868,7 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
     const int nrows = min(B - b0, 4);
     const int kbase = wave * KW;
     const float* whh = dir ? whh_r : whh_f;
-    if (FOLLOW && tid == 0) { phase = 0; fsync[0] = 0; fsync[1] = 0; }          // in front of chain_is_xcd_local's barriers
     const bool local = chain_is_xcd_local(ids + chain * 32, members, member, status, health, (unsigned*)(lds + 8 * 4 * RP), kHandoffSentinel) && !(force_wt & 1);
-    if constexpr (FOLLOW) {
-        if (tid >= 512) {
-            // waves 8 - 11: the next layer's x-projection (xproj_follow_waves above); two barriers per step of the chain, in step
-            const SeqRows fsr = seq_rows(lens, T, B, bt, packed_rows);
-            if (!seq_rows_fit(fsr, packed_rows)) return;
-            const int fTc = fsr.steps;
-            int joined = 0;
-            auto yield = [&]() {
-                if (joined < fTc && __hip_atomic_load(&phase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > joined) {
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_s_barrier();
-                    ++joined;
-                }
-            };
-            if (fa.mask) xproj_follow_waves<true>(fa, y, panel, fsync, fsr, dir, nrows, chain, member, local, joined, yield, status, health);
-            else xproj_follow_waves<false>(fa, y, panel, fsync, fsr, dir, nrows, chain, member, local, joined, yield, status, health);
-            while (joined < fTc) {
-                yield();
-                __builtin_amdgcn_s_sleep(2);
-            }
-            return;
-        }
-        __builtin_amdgcn_s_setprio(3);                // the chain is the latency-bound half of the workgroup
-    }
 
     // resident B operand: column 64*cb + lane of the workgroup's 128 = (gate, local unit) = (col >> 5, col & 31)
     f32x4 wv[2][NL];
@@ -1156,7 +925,8 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
     auto x_load = [&](int st) {
         const int tt = dir == 0 ? st : Tc - 1 - st;
         float v = *(const float*)(xproj_d + tt * xstep + xvoff);
-        // second addend: the other source direction's plane of the layer below (xproj_follow_waves writes one plane per direction)
+        // xproj2 is ALWAYS null (no caller has a second x-projection plane to add).  The test and the never-taken load stay because the
+        // sweep measured 2.6 % slower without them (profiles/follow_removed_ab.txt), although it then executes fewer instructions
         if (xproj2_d) v += *(const float*)(xproj2_d + tt * xstep + xvoff);
         return v;
     };
@@ -1167,9 +937,6 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
         for (int i = 0; i < NL; ++i) asm volatile("" : "+v"(wv[cb][i]));      // complete before the loop (see lstm_fwd_chain4v)
 
     LSTM_STAMP_DECL;
-#ifdef VOCR_FOLLOW_PROBE
-    if (FOLLOW && tid == 0 && member == 0 && chain < 2) fa.dbg[chain * 64 + 28] = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int step = s0; step < s1; ++step) {
         const int t = dir == 0 ? step : Tc - 1 - step;
         LSTM_STAMP(7);
@@ -1202,7 +969,6 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
             }
         }
         LSTM_STAMP(0);              // own slice of h_{t-1} arrived (polls)
-        if (FOLLOW && tid == 0) __hip_atomic_store(&phase, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // followers: to the barriers
         xn = x_load(step + 1 < Tc ? step + 1 : step);          // behind the polls: loads return in order
         if (step > 0) {
             static_for<NL>([&](auto bc) {
@@ -1262,22 +1028,6 @@ __global__ __launch_bounds__(FOLLOW ? 768 : 512) void lstm_fwd_chain4w(const flo
         if (tid < 128 && lane == 0) __hip_atomic_store(&sig[wave], step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         LSTM_STAMP(5);              // cell update + stores issued (waves 0, 1)
     }
-#ifdef VOCR_FOLLOW_PROBE
-    if (FOLLOW && tid == 0 && member == 0 && chain < 2) fa.dbg[chain * 64 + 29] = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (FOLLOW && tid < 128) {      // this member's last rows are out: the followers' last units wait for all 16 members of the chain
-        __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): this cell wave's stores have landed
-        if (lane == 0) {
-            if (!local) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_fetch_and(fa.done + chain * 32 + 16 + member, ~(1u << wave), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-#if defined(VOCR_LSTM_STAMPS) && defined(VOCR_FOLLOW_PROBE)
-    if (lane == 0 && (wave == 0 || wave == 7) && fa.dbg && blockIdx.x == 0) {
-        unsigned long long* o = fa.dbg + 256 + (wave == 7) * 8;
-        for (int k = 0; k < 8; ++k) o[k] = st_acc[k];
-    }
-#endif
 #ifdef VOCR_LSTM_STAMPS
     if (lane == 0 && (wave == 0 || wave == 7) && g_lstm_stamp_out) {
         unsigned long long* o = g_lstm_stamp_out + ((size_t)blockIdx.x * 2 + (wave == 7)) * 8;
@@ -2042,27 +1792,12 @@ bool launch_fwd_fast(int rt, dim3 grid, hipStream_t s, const float* xproj, const
     return false;
 }
 
-
-// ------------------------------------------------------------------------------------------------ x-projection behind the sweep
-// (the follower itself: xproj_follow_waves in front of lstm_fwd_chain4w)
-__global__ __launch_bounds__(256) void lstm_xproj_pack_kernel(const float* __restrict__ w_f, const float* __restrict__ w_r, float* __restrict__ wpack, int H) {
-    // wpack[src dir d][column tile ct (8H/32)][chunk j (H/8)][lane][4]: lane (c = lane & 31, hh = lane >> 5) holds
-    // W[32 ct + c][d*H + 8j + 4hh .. +3], W = [w_f; w_r] ([8H][2H])
-    const long piece = (long)blockIdx.x * 256 + threadIdx.x;
-    const int lane = piece & 63;
-    const long rest = piece >> 6;
-    const int nj = H / 8, nct = 8 * H / 32;
-    const int j = rest % nj, ct = (rest / nj) % nct, d = rest / ((long)nj * nct);
-    if (d >= 2) return;
-    const int col = 32 * ct + (lane & 31);
-    const float* w = col < 4 * H ? w_f + (long)col * 2 * H : w_r + (long)(col - 4 * H) * 2 * H;
-    ((f32x4*)wpack)[piece] = *(const f32x4*)(w + d * H + 8 * j + 4 * (lane >> 5));
-}
-
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-// workgroups of 256 threads that are certainly co-resident: one per CU (a persistent sweep deadlocks if a
-// workgroup it waits for is not running; the kernels need < 1/4 of a CU's registers and LDS, so one per CU is safe)
+// workgroups that are certainly co-resident: one per CU, provided nothing else holds the CU.  The 256-thread chain sweeps leave room
+// beside them; the wide sweeps do not: 8 waves of about 170 VGPRs fill a CU's registers to the point that a second such workgroup,
+// or another kernel's resident waves, keeps one off it.  A sweep whose grid is not wholly resident does not hang: every wait is a
+// bounded spin that raises the health word (raise_timeout)
 int resident_workgroup_capacity() {
     static int cus[64] = {0};
     int dev = 0;
@@ -2164,7 +1899,7 @@ static bool lstm_packed_kind_ok(int b, int h);
 
 static int lstm_fwd_impl(const float* xproj, const float* whh_fwd, const float* whh_rev, const int32_t* lens, float* y,
                          float* gates, float* cell, void* workspace, int t, int b, int h, int step_begin, int step_end,
-                         int packed_rows, int32_t* health, void* stream, const float* xproj2 = nullptr, const FollowArgs* follow = nullptr) {
+                         int packed_rows, int32_t* health, void* stream) {
     VOCR_CHECK_ARG(xproj && whh_fwd && whh_rev && lens && y && gates && cell && workspace, "vocr_lstm_fwd: null pointer");
     VOCR_CHECK_ARG(t > 0 && b > 0 && b <= 64 && h > 0 && h % 16 == 0, "vocr_lstm_fwd: need 1<=B<=64 and H%%16==0 (B=%d H=%d)", b, h);
     VOCR_CHECK_ARG(0 <= step_begin && step_begin < step_end && step_end <= t, "vocr_lstm_fwd: bad step range [%d, %d) of %d", step_begin, step_end, t);
@@ -2184,8 +1919,6 @@ static int lstm_fwd_impl(const float* xproj, const float* whh_fwd, const float* 
                        "vocr_lstm_fwd_packed: the packed row layout needs a 4-row chain sweep (ask vocr_lstm_packed_supported; B=%d H=%d)", b, h);
         VOCR_CHECK_ARG(packed_rows % 4 == 0 && packed_rows >= 4 * (1 + 2 * ((b + 3) / 4)), "vocr_lstm_fwd_packed: bad row count %d", packed_rows);
     }
-    VOCR_CHECK_ARG((!xproj2 && !follow) || (kind == SWEEP_WIDE4 && step_begin == 0 && step_end == t),
-                   "vocr_lstm_fwd_lead: two-plane x-projections / a follower need the wide 4-row chain sweep (ask vocr_lstm_follow_supported; B=%d H=%d)", b, h);
     if (kind != SWEEP_STEP) {
         // arrival flags: [chain <= 8][32 workgroups] at [0..255], XCC ids at [256..511]; status words at [512..]
         unsigned* flags = (unsigned*)workspace;
@@ -2201,24 +1934,8 @@ static int lstm_fwd_impl(const float* xproj, const float* whh_fwd, const float* 
             if (lstm_fwd_selfval_prep(blk, (size_t)4 * 2 * nt4 * 4 * h * sizeof(float), step_begin == 0, s) != VOCR_OK) return VOCR_ELAUNCH;
             if (kind == SWEEP_WIDE4) {
                 static const int nap4w = VOCR_EXPERIMENT_INT("VOCR_LSTM_NAP", 0);      // -1: polls start at once (experiments)
-                if (follow) {
-                    // waves 8 - 11 of every workgroup: the next layer's x-projection (xproj_follow_waves); 128 KB of dynamic LDS for their panel
-                    constexpr int kPanelBytes = 128 * 64 * 4 * 4;
-                    static VocrPerDevice lds_set;
-                    const void* const big[] = {(const void*)lstm_fwd_chain4w<8, true>};
-                    if (vocr_allow_dynamic_lds(big, 1, kPanelBytes, &lds_set, "vocr_lstm_fwd_lead") != VOCR_OK) return VOCR_ELAUNCH;
-                    FollowArgs fa = *follow;
-                    fa.done = blk;
-                    fa.dbg = (unsigned long long*)workspace;
-#ifdef VOCR_FOLLOW_PROBE
-                    fa.mode = getenv("VOCR_FOLLOW_MODE") ? atoi(getenv("VOCR_FOLLOW_MODE")) : 0;
-#endif
-                    lstm_fwd_chain4w<8, true><<<256, 768, kPanelBytes, s>>>(xproj, whh_fwd, whh_rev, lens, y, gates, cell, hx, blk, blk + 512, hword, t, b, nt4, fwt, step_begin,
-                                                                           step_end, nap4w, packed_rows, xproj2, fa);
-                } else {
-                    lstm_fwd_chain4w<8, false><<<256, 512, 0, s>>>(xproj, whh_fwd, whh_rev, lens, y, gates, cell, hx, blk, blk + 512, hword, t, b, nt4, fwt, step_begin,
-                                                                  step_end, nap4w, packed_rows, xproj2, FollowArgs{nullptr, nullptr, nullptr, nullptr, nullptr, (unsigned long long*)workspace, 0});
-                }
+                lstm_fwd_chain4w<8><<<256, 512, 0, s>>>(xproj, whh_fwd, whh_rev, lens, y, gates, cell, hx, blk, blk + 512, hword, t, b, nt4, fwt, step_begin,
+                                                        step_end, nap4w, packed_rows, nullptr);
             } else {
                 const dim3 cg4((2 * nt4 > 8 ? 16 : 8) * (h / 16));
                 if (h == 512) lstm_fwd_chain4v<8><<<cg4, 256, 0, s>>>(xproj, whh_fwd, whh_rev, lens, y, gates, cell, hx, blk, blk + 512, hword, t, b, nt4, fwt, step_begin, step_end, packed_rows);
@@ -2283,41 +2000,6 @@ extern "C" int vocr_lstm_fwd_packed(const float* xproj, const float* whh_fwd, co
                                     void* stream) {
     VOCR_CHECK_ARG(rows > 0, "vocr_lstm_fwd_packed: rows must be positive");
     return lstm_fwd_impl(xproj, whh_fwd, whh_rev, lens, y, gates, cell, workspace, t, b, h, 0, t, rows, health, stream);
-}
-
-// ---- the next layer's x-projection behind the sweep (lstm_xproj_follow above)
-extern "C" int vocr_lstm_follow_supported(int b, int h) {
-    if (b <= 16 || b > 32 || h != 512) return 0;
-    return lstm_sweep_kind(false, b, h, 8 * (h / 16) <= resident_workgroup_capacity()) == SWEEP_WIDE4 ? 1 : 0;
-}
-
-extern "C" size_t vocr_lstm_xproj_pack_bytes(int h) { return h > 0 ? (size_t)2 * 8 * h * h * sizeof(float) : 0; }
-
-extern "C" int vocr_lstm_xproj_pack(const float* w_ih_fwd, const float* w_ih_rev, float* wpack, int h, void* stream) {
-    VOCR_CHECK_ARG(w_ih_fwd && w_ih_rev && wpack, "vocr_lstm_xproj_pack: null pointer");
-    VOCR_CHECK_ARG(h == 512, "vocr_lstm_xproj_pack: H must be 512 (got %d)", h);
-    VOCR_CHECK_ARG(aligned16(w_ih_fwd) && aligned16(w_ih_rev) && aligned16(wpack), "vocr_lstm_xproj_pack: pointers must be 16-byte aligned");
-    const long pieces = 2l * (8 * h / 32) * (h / 8) * 64;
-    lstm_xproj_pack_kernel<<<(unsigned)(pieces / 256), 256, 0, (hipStream_t)stream>>>(w_ih_fwd, w_ih_rev, wpack, h);
-    VOCR_CHECK_LAUNCH("vocr_lstm_xproj_pack");
-    return VOCR_OK;
-}
-
-extern "C" int vocr_lstm_fwd_lead(const float* xproj, const float* xproj2, const float* whh_fwd, const float* whh_rev, const int32_t* lens,
-                                  float* y, float* gates, float* cell, void* workspace, int t, int b, int h, int rows,
-                                  const float* next_wpack, const float* next_bias, const float* y_mask, float* next_planes,
-                                  int32_t* health, void* stream) {
-    VOCR_CHECK_ARG(rows >= 0, "vocr_lstm_fwd_lead: rows must be >= 0 (0: dense)");
-    if (!next_wpack) {
-        VOCR_CHECK_ARG(!next_planes, "vocr_lstm_fwd_lead: next_planes without next_wpack");
-        return lstm_fwd_impl(xproj, whh_fwd, whh_rev, lens, y, gates, cell, workspace, t, b, h, 0, t, rows, health, stream, xproj2, nullptr);
-    }
-    VOCR_CHECK_ARG(next_planes, "vocr_lstm_fwd_lead: next_wpack without next_planes");
-    VOCR_CHECK_ARG(vocr_lstm_follow_supported(b, h), "vocr_lstm_fwd_lead: shape not taken (ask vocr_lstm_follow_supported; B=%d H=%d)", b, h);
-    VOCR_CHECK_ARG(aligned16(next_wpack) && aligned16(next_planes) && (!y_mask || aligned16(y_mask)), "vocr_lstm_fwd_lead: pointers must be 16-byte aligned");
-    VOCR_CHECK_ARG((rows ? (long)rows : (long)t * b) < (1l << 18), "vocr_lstm_fwd_lead: a plane of the next x-projection must stay below 2 GB (rows < 262144)");
-    const FollowArgs fa{next_wpack, y_mask, next_bias, next_planes, nullptr, nullptr, 0};
-    return lstm_fwd_impl(xproj, whh_fwd, whh_rev, lens, y, gates, cell, workspace, t, b, h, 0, t, rows, health, stream, xproj2, &fa);
 }
 
 // to_packed[t*B + b] = packed row of frame (t, b), or -1 where the packed layout has none (t >= the length of b's chain);

@@ -234,14 +234,10 @@ class CnnOcrModel(nn.Module):
         layers = [(self.lstm.layer(l, "")[1], self.lstm.layer(l, "")[2], self.lstm.layer(l, "")[3],
                    self.lstm.layer(l, "_reverse")[1], self.lstm.layer(l, "_reverse")[2], self.lstm.layer(l, "_reverse")[3])
                   for l in range(self.num_lstm_layers)]
-        # layers whose x-projection runs BESIDE the forward sweep of the layer below (ops.BiLstmLayerFn's `follow`): decided per batch
-        # below (the sweep kind depends on the batch size); their W_ih packs are weight-only work like the rest of the preparation
         H = self.num_lstm_hidden_units
-        follow_w = [(self.lstm.layer(l, "")[0], self.lstm.layer(l, "_reverse")[0]) for l in range(1, self.num_lstm_layers)]
-        may_follow = ops.lstm_follow_ok(x.shape[0], H, 2 * H, H)
         x6_w = [(self.lstm.layer(l, "")[0], self.lstm.layer(l, "_reverse")[0]) for l in range(self.num_lstm_layers)] \
             if ops.x6_layer_ok(1 << 10, x.shape[0], H, 0) else []
-        prep = ops.forward_prep(convs, layers, torch.is_grad_enabled(), f16, follow_w if may_follow else (), x6_w)
+        prep = ops.forward_prep(convs, layers, torch.is_grad_enabled(), f16, x6_w)
         a = x
         for i in range(self.num_rds_layers):
             conv = getattr(self.rapid_ds, "%02d-conv" % i)
@@ -310,8 +306,6 @@ class CnnOcrModel(nn.Module):
             hseq = ops.GatherRowsFn.apply(hseq, maps.to_dense, maps.to_packed, maps.rows)
         rows = maps.rows if maps is not None else 0
         drop = self.lstm.training and self.p_lstm_dropout > 0      # nn.LSTM reads its own .training flag
-        following = may_follow and 16 < b <= 32
-        pre = None
         x_bound = 0.0          # a bound on |hseq| where one is known: an LSTM layer's output lies in [-1, 1], times the drawn dropout's scale (fp16x3 splits use it)
         for l in range(self.num_lstm_layers):
             f = self.lstm.layer(l, "")
@@ -324,7 +318,7 @@ class CnnOcrModel(nn.Module):
             if b <= 64:
                 # one op per layer.  The inter-layer dropout rides inside it: an explicit mask, or - on packed rows - the drawn mask of the
                 # DENSE frame order moved through the row map, so that a frame's draw does not depend on whether the batch was packed
-                fol, mk = None, None
+                mk = None
                 if not last and self.dropout_masks is not None:
                     mk = self.dropout_masks[l].to(dev).reshape(T * b, -1)
                     if maps is not None:
@@ -332,23 +326,13 @@ class CnnOcrModel(nn.Module):
                 elif draw and maps is not None:
                     mk = ops.gather_rows(ops.dropout_mask(T * b, 2 * H, self.p_lstm_dropout, self.dropout_seed + self._dropout_calls, dev),
                                          maps.to_dense, maps.rows)
-                if following and not last:
-                    # layer l + 1's x-projection inside this layer's sweep (ops.BiLstmLayerFn's `follow`)
-                    nf, nr = self.lstm.layer(l + 1, ""), self.lstm.layer(l + 1, "_reverse")
-                    key = nf[1].data_ptr()
-                    if prep is not None:
-                        prep.wait()
-                    fol = {"w_ih": (nf[0], nr[0]), "out": [],
-                           "bias": prep.lstm[key][0] if prep is not None and key in prep.lstm else ops.lstm_bias_sum(nf[2], nf[3], nr[2], nr[3]),
-                           "wpack": prep.xpack.get(nf[0].data_ptr()) if prep is not None else None}
                 with prof_range("model.lstm.l%d" % l):
                     dp, ds = (self.p_lstm_dropout, self.dropout_seed + self._dropout_calls) if draw and mk is None else (0.0, 0)
                     hseq = ops.BiLstmLayerFn.apply(hseq, lens_dev, T, b, f[0], f[1], f[2], f[3], r[0], r[1], r[2], r[3], prep, True, dp, ds, rows,
-                                                   pre, fol, mk, x_bound)
+                                                   mk, x_bound)
                     # what the next layer reads: this layer's output, times 1 / (1 - p) where a mask we drew ourselves was applied (an explicit mask: unknown)
                     x_bound = 0.0 if (mk is not None and self.dropout_masks is not None) else \
                         (1.0 / (1.0 - self.p_lstm_dropout) if (dp > 0 or mk is not None) else 1.0)
-                pre = fol["out"][0] if fol is not None else None
                 continue
             with prof_range("model.lstm.l%d" % l):
                 hseq = self._bilstm_layer(hseq, lens_dev, out_w, T, b, f, r, prep)

@@ -85,14 +85,6 @@ def side_stream(device=None):
     return _side(device)["stream"]
 
 
-_LSTM_FOLLOW = _exp("VOCR_LSTM_FOLLOW", "0") == "1"          # measured slower than the GEMM in front of the next sweep: an experiment switch
-
-
-def lstm_follow_ok(b, h, din_next, h_next):
-    """Layer l+1's x-projection can run behind layer l's forward sweep (include/vocr.h: vocr_lstm_follow_supported)."""
-    return _LSTM_FOLLOW and h_next == h and din_next == 2 * h and bool(_lib.load().vocr_lstm_follow_supported(int(b), int(h)))
-
-
 def mark_side_pending(device=None):
     _side(device)["pending"] = True
 
@@ -194,7 +186,6 @@ class ForwardPrep(object):
     def __init__(self):
         self.packs = {}          # weight.data_ptr() -> (pack_fwd, pack_dgrad)
         self.lstm = {}           # w_hh_f.data_ptr() -> (bsum, wt_f, wt_r)
-        self.xpack = {}          # w_ih_f.data_ptr() -> W_ih of both directions in the follower's fragment order (vocr_lstm_xproj_pack)
         self.x6w = {}            # w_ih_f.data_ptr() -> (planes of [W_f; W_r] rows = gate rows, k = input: the x-projection's B;
                                  #                       planes of its transpose rows = input, k = gate rows: the data gradient's B or None)
         self.event = None        # everything done (the LSTM items come last: they are needed ~4 ms into the step)
@@ -213,22 +204,6 @@ class ForwardPrep(object):
             torch.cuda.current_stream().wait_event(ev)
 
 
-def lstm_bias_sum(b_ih_f, b_hh_f, b_ih_r, b_hh_r):
-    """[2, 4H]: b_ih + b_hh of both directions (what the x-projection adds)."""
-    H4 = b_ih_f.numel()
-    bsum = torch.empty(2, H4, dtype=torch.float32, device=b_ih_f.device)
-    call("vocr_add", _p(b_ih_f), _p(b_hh_f), _p(bsum[0]), H4, _stream())
-    call("vocr_add", _p(b_ih_r), _p(b_hh_r), _p(bsum[1]), H4, _stream())
-    return bsum
-
-
-def lstm_xproj_pack(w_ih_f, w_ih_r):
-    h = w_ih_f.shape[0] // 4
-    wpack = torch.empty(_lib.load().vocr_lstm_xproj_pack_bytes(h) // 4, dtype=torch.float32, device=w_ih_f.device)
-    call("vocr_lstm_xproj_pack", _p(w_ih_f), _p(w_ih_r), _p(wpack), h, _stream())
-    return wpack
-
-
 def x6_weight_planes(w_ih_f, w_ih_r, with_transpose):
     g4, din = w_ih_f.shape
     wk = x6_planes(w_ih_f, 2 * g4, din, True, din, x2=w_ih_r, seg=g4, axis=1)
@@ -236,9 +211,9 @@ def x6_weight_planes(w_ih_f, w_ih_r, with_transpose):
     return wk, wt
 
 
-def forward_prep(conv_weights, lstm_layers, with_transposes, f16=False, follow_layers=(), x6_layers=()):
+def forward_prep(conv_weights, lstm_layers, with_transposes, f16=False, x6_layers=()):
     """conv_weights: 4-D fp32 weights to pack (f16: into the fp16-operand kernels' packs); lstm_layers: [(w_hh_f, b_ih_f, b_hh_f, w_hh_r,
-    b_ih_r, b_hh_r), ...]; follow_layers: [(w_ih_f, w_ih_r), ...] of the layers whose x-projection runs behind the sweep below them;
+    b_ih_r, b_hh_r), ...];
     x6_layers: [(w_ih_f, w_ih_r), ...] of the layers whose GEMMs run as bf16x6 products (their weight planes are made here)."""
     if not _SIDE_ENABLED or _exp("VOCR_FWD_PREP", "1") != "1":
         return None
@@ -268,9 +243,6 @@ def forward_prep(conv_weights, lstm_layers, with_transposes, f16=False, follow_l
             if w_ih_f.shape[1] >= 512:
                 prep.x6w[w_ih_f.data_ptr()] = x6_weight_planes(w_ih_f, w_ih_r, with_transposes)
                 made.extend(t for t in prep.x6w[w_ih_f.data_ptr()] if t is not None)
-        for (w_ih_f, w_ih_r) in follow_layers:
-            prep.xpack[w_ih_f.data_ptr()] = lstm_xproj_pack(w_ih_f, w_ih_r)
-            made.append(prep.xpack[w_ih_f.data_ptr()])
         prep.event = torch.cuda.Event()
         prep.event.record(side)
     for t in made:
@@ -1003,14 +975,10 @@ class BiLstmLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, lens_dev, T, B, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, prep=None, direct_grads=True,
-                drop_p=0.0, drop_seed=0, rows=0, pre=None, follow=None, drop_mask=None, x_bound=0.0):
+                drop_p=0.0, drop_seed=0, rows=0, drop_mask=None, x_bound=0.0):
         """drop_p > 0: nn.LSTM's inter-layer dropout on this layer's OUTPUT (counter-based mask of vocr_dropout_fwd, as DropoutFn) -
         here so that its backward can ride on the backward sweep's read of dy instead of being a pass of its own.  drop_mask: the same
-        with a mask that already exists ([R, 2H], pre-scaled; explicit test masks, or vocr_dropout_mask's draw made ahead of the sweep).
-        pre: (plane0, plane1), this layer's x-projection as the two source-direction planes a follower behind the layer below wrote
-        (each [2, R, 4H]; x is then only kept for the backward).  follow: {"w_ih": (f, r) of the NEXT layer, "bias": its [2, 4H] bias
-        sums or None, "wpack": its vocr_lstm_xproj_pack or None, "out": list} - the next layer's x-projection runs inside this layer's
-        sweep (vocr_lstm_fwd_lead's follower waves) and its two planes are appended to follow["out"]."""
+        with a mask that already exists ([R, 2H], pre-scaled; explicit test masks, or vocr_dropout_mask's draw made ahead of the sweep)."""
         _need_gpu(x, lens_dev, w_ih_f, w_hh_f, w_ih_r, w_hh_r)
         x = _f32c(x)
         lib = _lib.load()
@@ -1019,7 +987,7 @@ class BiLstmLayerFn(torch.autograd.Function):
         dev = x.device
         R = int(rows) if rows else T * B              # rows of every sequence-side matrix of this layer
         assert x.shape[0] == R, (x.shape, R)
-        xproj = torch.empty(2, R, 4 * H, dtype=torch.float32, device=dev) if pre is None else None
+        xproj = torch.empty(2, R, 4 * H, dtype=torch.float32, device=dev)
         ctx.wt = None
         if prep is not None and w_hh_f.data_ptr() in prep.lstm:
             prep.wait()
@@ -1039,7 +1007,7 @@ class BiLstmLayerFn(torch.autograd.Function):
 
         ctx.x6 = x6_layer_ok(T, B, H, rows)
         ctx.x6_wt = None
-        if pre is None and ctx.x6 and din >= 512:
+        if ctx.x6 and din >= 512:
             # bf16x6: the operands as three exact bf16 planes, six bf16 MFMAs per product (include/vocr.h: vocr_gemm_x6)
             if prep is not None and w_ih_f.data_ptr() in prep.x6w:
                 wk, ctx.x6_wt = prep.x6w[w_ih_f.data_ptr()]
@@ -1047,29 +1015,11 @@ class BiLstmLayerFn(torch.autograd.Function):
                 wk, ctx.x6_wt = x6_weight_planes(w_ih_f, w_ih_r, torch.is_grad_enabled())
             xa = x6_planes(x, R, din, True, din, bound=x_bound)
             gemm_x6(xa, R, din, wk, 2 * G, din, R, 2 * G, din, xproj[0], G, c1=xproj[1], csplit=G, bias0=bsum[0], bias1=bsum[1])
-        elif pre is None:
+        else:
             # both directions' x-projections in one launch: 2 x (columns / 128) panels x row groups == the CU count
             gemm_pair(0, 0, 1, R, G, din, x, x, din, w_ih_f, w_ih_r, din, xproj[0], xproj[1], G, bias0=bsum[0], bias1=bsum[1])
         mask = drop_mask
-        if follow is not None:
-            # the NEXT layer's x-projection inside this layer's sweep (four more waves per workgroup: include/vocr.h, vocr_lstm_fwd_lead)
-            nf, nr = follow["w_ih"]
-            wpack = follow.get("wpack")
-            if wpack is None:
-                wpack = lstm_xproj_pack(nf, nr)
-            nbias = follow.get("bias")
-            if mask is None and drop_p and float(drop_p) > 0.0:
-                mask = torch.empty_like(y)
-                call("vocr_dropout_mask", _p(mask), mask.numel(), float(drop_p), int(drop_seed), _stream())
-            planes = torch.empty(2, 2, R, G, dtype=torch.float32, device=dev)
-            p0, p1 = (pre if pre is not None else (xproj, None))
-            call("vocr_lstm_fwd_lead", _p(p0), _p(p1), _p(w_hh_f), _p(w_hh_r), _p(lens_dev), _p(y), _p(gates), _p(cell), _p(ws), T, B, H, R if rows else 0,
-                 _p(wpack), _p(nbias), _p(mask), _p(planes), _p(health(dev)), _stream())
-            follow["out"].append((planes[0], planes[1]))
-        elif pre is not None:
-            call("vocr_lstm_fwd_lead", _p(pre[0]), _p(pre[1]), _p(w_hh_f), _p(w_hh_r), _p(lens_dev), _p(y), _p(gates), _p(cell), _p(ws), T, B, H,
-                 R if rows else 0, None, None, None, None, _p(health(dev)), _stream())
-        elif rows:
+        if rows:
             call("vocr_lstm_fwd_packed", _p(xproj), _p(w_hh_f), _p(w_hh_r), _p(lens_dev), _p(y), _p(gates), _p(cell), _p(ws), T, B, H, R,
                  _p(health(dev)), _stream())
         else:
@@ -1081,7 +1031,7 @@ class BiLstmLayerFn(torch.autograd.Function):
         ctx.b_refs = (b_ih_f, b_hh_f, b_ih_r, b_hh_r)
         out = y
         if mask is not None:
-            # what the NEXT layer's weight gradient multiplies (the follower waves applied the mask on their own read of y)
+            # a mask that already exists (an explicit one, or the draw made ahead of a packed sweep): one multiply, nothing to draw
             out = torch.empty_like(y)
             call("vocr_mul", _p(y), _p(mask), _p(out), y.numel(), _stream())
         elif drop_p and float(drop_p) > 0.0:
@@ -1204,13 +1154,13 @@ class BiLstmLayerFn(torch.autograd.Function):
             with torch.cuda.stream(side):
                 weight_grads(sinks)                 # under the next layer's persistent sweep
             mark_side_pending()
-            return (dx, None, None, None) + (None,) * 17
+            return (dx, None, None, None) + (None,) * 15
         if direct:
             weight_grads(sinks)
-            return (dx, None, None, None) + (None,) * 17
+            return (dx, None, None, None) + (None,) * 15
         outs = [torch.empty_like(p) for p in params]
         weight_grads(outs)
-        return (dx, None, None, None) + tuple(outs) + (None,) * 9
+        return (dx, None, None, None) + tuple(outs) + (None,) * 7
 
 
 # ------------------------------------------------------------------------------------------------ CTC
