@@ -615,7 +615,8 @@ int vocr_ctc_keyword_scores(const float* logits, const int32_t* lens, int t, int
  * The excluded term is CTC's repeat rule: the same class twice in a row needs a blank between, the route through W.  It is evaluated as
  * lse(prefix, suffix) over the class-sorted incoming arcs, never as a subtraction.  For a DETERMINISTIC automaton every labelling has
  * one state sequence and P is exactly the probability that the labelling is accepted; for a non-deterministic one it is the sum over
- * (frame path, automaton path) pairs.  WHAT IT IS NOT: there are no weights on the arcs (no language model), and the best
+ * (frame path, automaton path) pairs.  WHAT IT IS NOT: this entry has no weights on the arcs (vocr_ctc_grammar_scores_weighted below
+ * has), and the best
  * score is the maximum over single PATHS through the product (frame path and automaton path), not the most probable accepted
  * labelling.  The best path is the same recursion with max, a back pointer per frame and cell in the workspace; a candidate replaces
  * the choice only when strictly greater - W: stay, then the incoming arcs in arc order; A: stay, then W[src], then the incoming arcs in
@@ -641,6 +642,33 @@ int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int
                             float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- weighted grammars: the same sweep over an automaton whose arcs and accepting states carry weights ---- */
+/* vocr_ctc_grammar_scores with two more device fp32 tables: arc_logw[a], one natural-log weight per arc (the arcs' own order and
+ * offsets), and final_logw[s], one per state (the states' order and offsets), read for ACCEPTING states only.  The weight w(rho) of an
+ * automaton path rho is the sum of its arcs' weights plus the final weight of its last state.  Sum pass: ln Z = ln of the sum of
+ * P(pi | x) * exp(w(rho)) over all (frame path pi, automaton path rho) pairs whose labelling rho accepts - a probability only when the
+ * weights normalise; max pass: max of ln P(pi | x) + w(rho).
+ *   t = 0: W[0] = lp_0(blank), A[a] = lp_0(cls_a) + w_a if src_a = 0, everything else -inf;
+ *   t > 0: W'[s] = lp_t(blank) + lse(W[s], A[a'] for every a' into s)                                              (unchanged)
+ *          A'[a] = lp_t(cls_a) + lse(A[a], w_a + lse(W[src_a], A[a'] into src_a of another class));
+ *   end  : lse(W[s] + f_s for accepting s, A[a] + f_dst_a for accepting dst_a);   lens[b] = 0: f_0 if state 0 accepts.
+ * An arc's weight is paid once per traversal - never on a stay, and again each time a self-loop is re-entered through its W cell.  (The
+ * kernels pay it when the arc cell is LEFT, which shifts every arc cell by a constant of its own and changes neither ln Z nor the
+ * maxima.)  The max pass keeps the tie rule and the back pointers: the same candidates in the same order, each with its weight added.
+ * Both tables must be finite: an automaton with a NaN or infinite arc weight, or such a final weight on an accepting state, breaks a
+ * rule like a mis-sorted arc and poisons its own column.  The two tables go together (one without the other: VOCR_EINVAL before any
+ * launch); BOTH NULL runs the unweighted code: the bits of vocr_ctc_grammar_scores.  Limits, outputs and workspace are those of
+ * vocr_ctc_grammar_scores (vocr_ctc_grammar_weighted_workspace_bytes returns the same figure): the weights are staged in LDS with the
+ * plan where they fit beside the rows, else read from global memory, one coalesced float per arc cell and frame. */
+size_t vocr_ctc_grammar_weighted_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_best);
+int vocr_ctc_grammar_scores_weighted(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                     const int32_t* g_state_off, const int32_t* g_arc_off, int g,
+                                     const int32_t* arc_src, const int32_t* arc_cls, const int32_t* arc_dst,
+                                     const int32_t* accept, const float* arc_logw, const float* final_logw,
+                                     int max_states, int max_arcs,
+                                     float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- grammar-constrained CTC training: the gradient of the match score (graph-based temporal classification) ---- */
 /* out_logp[b] = ln P(line b's labelling is accepted by automaton which[b]) and dlogits = d/dlogits sum_b weights[b] * ln P_b.  The
  * automaton tables, their sort order (dst, class, src), classes, blank, the repeat rule and the validity rules are exactly those of
@@ -664,7 +692,7 @@ int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int
  * P_t(c) = 0 never yields NaN or inf.  No floating-point atomics: the per-class occupancy sum runs over a class-sorted arc index built
  * on the device, one wave per class, in a fixed order; results are bit-identical from run to run, and a line's rows depend on that
  * line and its automaton alone.  weights (device fp32 [B]) and dlogits ([T][B][V]) are both NULL or both given; both NULL: scores
- * only, nothing is stored and no backward sweep runs.  WHAT IT IS NOT: no weights on the arcs, no best path (vocr_ctc_grammar_scores
+ * only, nothing is stored and no backward sweep runs.  WHAT IT IS NOT: weighted (vocr_ctc_grammar_grad_weighted below is), a best path (vocr_ctc_grammar_scores
  * has it), and the forward rows are STORED: t * b * (max_states + max_arcs) * 4 bytes of workspace, which must stay within 2 GiB -
  * the caller cuts the batch (every line is independent).  Limits: those of vocr_ctc_grammar_scores (2 <= v <= 256, g >= 1,
  * t * b * g < 2^31, max_states + max_arcs <= 8192) plus that lattice.  Workspace (16-byte aligned: class log-probabilities, the plan,
@@ -677,6 +705,23 @@ int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b
                           const int32_t* accept, int max_states, int max_arcs,
                           const int32_t* which, const float* weights, float* out_logp, float* dlogits,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same under a weighted automaton (arc_logw, final_logw: vocr_ctc_grammar_scores_weighted): out_logp[b] = ln Z_b, with the bits of
+ * vocr_ctc_grammar_scores_weighted's out_logp[b][which[b]], and dlogits = d/dlogits sum_b weights[b] * ln Z_b.  The occupancy form
+ * above is unchanged; alpha and bhat carry the weights.  The backward sweep runs the same recursion over the mirrored automaton, where
+ * "enter arc a" is the original's "leave arc a": the mirror kernel permutes the weights with the arcs, the mirror's start weights are
+ * the original's final weights and the original's start state has none, and every arc weight and every final weight of a path is
+ * counted exactly once in alpha_t(c) + bhat_t(c), for every cell and frame - so every frame's occupancies still sum to 1.  There is no
+ * gradient with respect to the weights themselves.  The two tables go together; both NULL runs the unweighted code, the bits of
+ * vocr_ctc_grammar_grad.  The workspace holds the mirrored weights too: vocr_ctc_grammar_grad_weighted_workspace_bytes. */
+size_t vocr_ctc_grammar_grad_weighted_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad);
+int vocr_ctc_grammar_grad_weighted(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                   const int32_t* g_state_off, const int32_t* g_arc_off, int g,
+                                   const int32_t* arc_src, const int32_t* arc_cls, const int32_t* arc_dst,
+                                   const int32_t* accept, const float* arc_logw, const float* final_logw,
+                                   int max_states, int max_arcs,
+                                   const int32_t* which, const float* weights, float* out_logp, float* dlogits,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- grammar-constrained CTC prefix beam search: the most probable labellings a deterministic automaton accepts ---- */
 /* vocr_ctc_beam_search - the same inputs, classes, optional character n-gram tables, score formula, total order, pruning, limits
@@ -695,7 +740,7 @@ int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b
  * that is empty, reversed or past g_state_off[g] gives that line no hypothesis, a next state outside the automaton counts as no arc, a
  * negative distance as "cannot accept"; none of them becomes a load address.  Under the one-state automaton that accepts everything
  * the search takes the decisions of vocr_ctc_beam_search.  WHAT IT IS NOT: exact beyond the beam (a labelling whose prefix fell out
- * of the beam is lost, as in every beam search), weighted (no weights on the arcs; the LM is the character n-gram), or
+ * of the beam is lost, as in every beam search), weighted (vocr_ctc_grammar_beam_search_weighted below is), or
  * non-deterministic.  There is no limit on the automaton's size but the memory of the dense tables (states * v * 4 bytes).  Only
  * integer LDS atomics; results are bit-identical from run to run.  Bad arguments (g < 1, a NULL table, a short workspace) fail with
  * VOCR_EINVAL before any launch.  Workspace from vocr_ctc_grammar_beam_workspace_bytes (0 for an unsupported shape). */
@@ -706,6 +751,25 @@ int vocr_ctc_grammar_beam_search(const float* logits, const int32_t* lens, int t
                                  int lm_states, int lm_start, float lm_weight, float insertion_bonus, float prune_logp,
                                  int32_t* out_labels, int32_t* out_lens, float* out_scores,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same under a weighted automaton: dfa_logw[states][v] (device fp32, dfa_next's indexing: the natural-log weight of the arc from
+ * the state on class c; only canonical columns that have an arc are read) and dfa_final[states] (the final weight, read for accepting
+ * states).  The automaton is deterministic, so a prefix has one state and ONE accumulated weight gacc, carried by its beam, and the
+ * exact prefix merge stays valid.  A candidate's rank adds grammar_weight * gacc_k for a stay and grammar_weight * (gacc_k +
+ * dfa_logw[state_k][c]) for an extension; the final rank adds grammar_weight * (gacc + dfa_final[state]).  The distance rule, the
+ * merge, top-K and the total order are untouched.  out_scores keeps its three columns (total, acoustic, LM); total includes the
+ * grammar term, and out_grammar[B][nbest] (device fp32, NULL: not wanted) is the hypothesis's raw weight gacc + dfa_final[state], 0
+ * for a rank the search did not fill.  grammar_weight must be finite.  An arc whose weight is NaN or infinite counts as no arc, an
+ * accepting state with such a final weight as not accepting.  dfa_logw and dfa_final go together (one without the other: VOCR_EINVAL
+ * before any launch); BOTH NULL runs the unweighted search - the bits of vocr_ctc_grammar_beam_search, out_grammar zeros.  Limits and
+ * workspace: vocr_ctc_grammar_beam_search's. */
+int vocr_ctc_grammar_beam_search_weighted(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon, int beam,
+                                          int nbest, const int32_t* g_state_off, const int32_t* dfa_next, const int32_t* dfa_dist,
+                                          const float* dfa_logw, const float* dfa_final, int g, const int32_t* which,
+                                          const float* lm_logp, const int32_t* lm_next, const float* lm_eos, int lm_states, int lm_start,
+                                          float lm_weight, float grammar_weight, float insertion_bonus, float prune_logp,
+                                          int32_t* out_labels, int32_t* out_lens, float* out_scores, float* out_grammar,
+                                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- edit statistics: compute_cer_wer of test_on_val (src/textutils.py:264-351, src/train_cnn_lstm.py:32-100) and src/edit_dist_trace.py ---- */
 /* Levenshtein statistics (unit costs) of np (hypothesis, reference) pairs that are already on the device: distances and lengths over

@@ -119,10 +119,16 @@ SIGNATURES = {
     "vocr_ctc_keyword_scores": (I, [P, P, I, I, I, P, P, P, P, I, I, I, P, P, P, P, Z, P]),
     "vocr_ctc_grammar_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
     "vocr_ctc_grammar_scores": (I, [P, P, I, I, I, P, P, P, I, P, P, P, P, I, I, P, P, P, P, I, P, Z, P]),
+    "vocr_ctc_grammar_weighted_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
+    "vocr_ctc_grammar_scores_weighted": (I, [P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, I, I, P, P, P, P, I, P, Z, P]),
     "vocr_ctc_grammar_grad_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
     "vocr_ctc_grammar_grad": (I, [P, P, I, I, I, P, P, P, I, P, P, P, P, I, I, P, P, P, P, P, Z, P]),
+    "vocr_ctc_grammar_grad_weighted_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
+    "vocr_ctc_grammar_grad_weighted": (I, [P, P, I, I, I, P, P, P, I, P, P, P, P, P, P, I, I, P, P, P, P, P, Z, P]),
     "vocr_ctc_grammar_beam_workspace_bytes": (Z, [I, I, I, I, I]),
     "vocr_ctc_grammar_beam_search": (I, [P, P, I, I, I, P, I, I, P, P, P, I, P, P, P, P, I, I, F, F, F, P, P, P, P, Z, P]),
+    "vocr_ctc_grammar_beam_search_weighted": (I, [P, P, I, I, I, P, I, I, P, P, P, P, P, I, P, P, P, P, I, I, F, F, F, F, P, P, P, P, P, Z,
+                                                  P]),
     "vocr_edit_stats_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
     "vocr_edit_stats": (I, [P, P, I, I, I, P, P, I, I, I, P, I, P, P, I, I, P, P, P, I, P, Z, P]),
     "vocr_augment_workspace_bytes": (Z, [I, I, I, I]),

@@ -53,16 +53,35 @@ __device__ __forceinline__ int lower_bound(int lo, int hi, int want, Key key) {
     return lo;
 }
 
+// What the weights add to a kernel's arguments; empty without them (the pattern of ctc_beam.hip's Dfa<GRAMMAR>).
+template <bool WT>
+struct GWeights {};
+template <>
+struct GWeights<true> {
+    const float* __restrict__ arc;              // one natural-log weight per arc, in the order of the arcs the kernel is given
+    const float* __restrict__ fin;              // one per state (the caller's state order), read for accepting states only
+    const int32_t* __restrict__ accept;
+};
+
+__device__ __forceinline__ bool g_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }   // false for NaN and +-inf
+
+// bytes of one automaton's plan as g_stage lays it out in LDS (the weights, where they are staged too, follow it)
+__host__ __device__ constexpr size_t staged_plan_bytes(int max_states, int max_arcs) {
+    return (((size_t)max_arcs * sizeof(int4) + (size_t)max_states * sizeof(int2) + (size_t)big_stride(max_arcs) * sizeof(int32_t)) + 15) &
+           ~(size_t)15;
+}
+
 // grid.x = G, 256 threads.  flags[k] = 1 for an automaton that breaks a rule (nothing else is written for it).  st[k][s] = {first,
 // end} of the incoming arcs of s; meta[k][a] = {src, class column, xa, xb}: the other classes' incoming arcs of src are those before
 // xa (read: the exclusive prefix at xa; -1: none) and from xb on (the inclusive suffix at xb; -1: none).  arc_stride = 0: automaton k's
 // arcs lie at g_arc_off[k] of the arc arrays (the caller's tables); > 0: at k * arc_stride (the mirrored tables in the workspace).
+template <bool WT>
 __global__ __launch_bounds__(256) void grammar_plan_kernel(const int32_t* __restrict__ canon, const int32_t* __restrict__ g_state_off,
                                                            const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_src,
                                                            const int32_t* __restrict__ arc_cls, const int32_t* __restrict__ arc_dst, int V,
                                                            int max_states, int max_arcs, int arc_stride,
                                                            int32_t* __restrict__ flags, int2* __restrict__ st, int4* __restrict__ meta,
-                                                           int32_t* __restrict__ big_all) {
+                                                           int32_t* __restrict__ big_all, GWeights<WT> GW) {
     __shared__ int s_wcnt[4];
     __shared__ int s_base;
     const int k = blockIdx.x, tid = threadIdx.x;
@@ -86,6 +105,10 @@ __global__ __launch_bounds__(256) void grammar_plan_kernel(const int32_t* __rest
             const int cp = cls_of(i - 1);
             bad |= dst[i - 1] > dst[i] || (dst[i - 1] == dst[i] && (cp > c || (cp == c && src[i - 1] > src[i])));
         }
+        if constexpr (WT) bad |= !g_finite(GW.arc[base + i]);
+    }
+    if constexpr (WT) {                                            // a weight that is NaN or infinite breaks a rule like a mis-sorted arc
+        for (int i = tid; i < S; i += 256) bad |= GW.accept[s0 + i] != 0 && !g_finite(GW.fin[s0 + i]);
     }
     if (__syncthreads_or(bad)) {
         if (tid == 0) flags[k] = 1;
@@ -188,38 +211,47 @@ __device__ __forceinline__ void g_store(float* __restrict__ p, int i, const GAcc
 }
 
 // ... read back: the value, and in the max pass the arc it came from (-1: none)
-template <bool BEST>
-__device__ __forceinline__ float g_read(const float* __restrict__ p, int i, const float* __restrict__ A, int& arc) {
+template <bool BEST, bool WT>
+__device__ __forceinline__ float g_read(const float* __restrict__ p, int i, const float* __restrict__ A, const float* __restrict__ aw,
+                                        int& arc) {
     arc = -1;
     if (i < 0) return NEG_INF;
     if (!BEST) return p[i];
     arc = reinterpret_cast<const int*>(p)[i];
-    return arc < 0 ? NEG_INF : A[arc];
+    if (arc < 0) return NEG_INF;
+    return WT ? A[arc] + aw[arc] : A[arc];
+}
+
+// what arc cell i hands on when it is LEFT: the weighted sweeps pay an arc's weight there (a stay pays nothing)
+template <bool WT>
+__device__ __forceinline__ float g_out(const float* __restrict__ A, const float* __restrict__ aw, int i) {
+    return WT ? A[i] + aw[i] : A[i];
 }
 
 // the scans of one state's incoming arcs [lo, hi) by one lane
-template <bool BEST>
-__device__ __forceinline__ void lane_scan(const float* __restrict__ A, float* __restrict__ pre, float* __restrict__ suf, int lo, int hi) {
+template <bool BEST, bool WT>
+__device__ __forceinline__ void lane_scan(const float* __restrict__ A, const float* __restrict__ aw, float* __restrict__ pre,
+                                          float* __restrict__ suf, int lo, int hi) {
     GAcc acc = g_none();
     for (int i = lo; i < hi; ++i) {
         g_store<BEST>(pre, i, acc);
-        acc = g_join<BEST>(acc, g_elem(A[i], i));
+        acc = g_join<BEST>(acc, g_elem(g_out<WT>(A, aw, i), i));
     }
     acc = g_none();
     for (int i = hi - 1; i >= lo; --i) {
-        acc = g_join<BEST>(g_elem(A[i], i), acc);
+        acc = g_join<BEST>(g_elem(g_out<WT>(A, aw, i), i), acc);
         g_store<BEST>(suf, i, acc);
     }
 }
 
 // ... and by a whole wave (lo, hi wave-uniform): 64 arcs at a time, Hillis-Steele over the lanes, the earlier chunks carried along
-template <bool BEST>
-__device__ __forceinline__ void wave_scan(const float* __restrict__ A, float* __restrict__ pre, float* __restrict__ suf, int lo, int hi,
-                                          int lane) {
+template <bool BEST, bool WT>
+__device__ __forceinline__ void wave_scan(const float* __restrict__ A, const float* __restrict__ aw, float* __restrict__ pre,
+                                          float* __restrict__ suf, int lo, int hi, int lane) {
     GAcc carry = g_none();
     for (int c0 = lo; c0 < hi; c0 += 64) {
         const int i = c0 + lane;
-        GAcc x = i < hi ? g_elem(A[i], i) : g_none();
+        GAcc x = i < hi ? g_elem(g_out<WT>(A, aw, i), i) : g_none();
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const GAcc u = g_shfl_up<BEST>(x, o);
@@ -233,7 +265,7 @@ __device__ __forceinline__ void wave_scan(const float* __restrict__ A, float* __
     carry = g_none();
     for (int c1 = hi; c1 > lo; c1 -= 64) {
         const int i = c1 - 64 + lane;
-        GAcc x = i >= lo ? g_elem(A[i], i) : g_none();
+        GAcc x = i >= lo ? g_elem(g_out<WT>(A, aw, i), i) : g_none();
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const GAcc u = g_shfl_down<BEST>(x, o);
@@ -272,17 +304,31 @@ __device__ __forceinline__ GView g_stage(const GView& g, float* at, int max_stat
     return {g.S, g.N, ls, lm, lb, g.nbig};
 }
 
+// ... and the automaton's arc weights behind the staged plan (stage & 2: they fit too); else they are read where they lie, one
+// coalesced float per arc cell and frame.  No barrier of its own: call it before g_stage, whose barrier covers it.
+__device__ __forceinline__ const float* g_stage_weights(const float* __restrict__ aw, int E, int stage, float* stage_at, int max_states,
+                                                        int max_arcs, int tid, int NT) {
+    if (!(stage & 2)) return aw;
+    float* lw = stage_at + staged_plan_bytes(max_states, max_arcs) / sizeof(float);
+    for (int i = tid; i < E; i += NT) lw[i] = aw[i];
+    return lw;
+}
+
 // The first frame's row from its class log-probabilities lpr (in LDS): the W cell of every start state and the arc cells that leave
 // one.  start = NULL: state 0 alone (the forward sweep); else start[s] != 0 (the mirrored sweep: every accepting state).
+// WT: a start state s of the mirrored sweep carries fw[s], the original's final weight; state 0 of the forward sweep carries none.
+template <bool WT>
 __device__ __forceinline__ void g_first_row(const GView& g, float* __restrict__ row, const float* __restrict__ lpr,
-                                            const int32_t* __restrict__ start, int tid, int NT) {
+                                            const int32_t* __restrict__ start, const float* __restrict__ fw, int tid, int NT) {
     for (int c = tid; c < g.N; c += NT) {
         float v = NEG_INF;
         if (c < g.S) {
             if (start ? start[c] != 0 : c == 0) v = lpr[0];
+            if (WT && start && v != NEG_INF) v += fw[c];
         } else {
             const int4 m = g.meta[c - g.S];
             if (start ? start[m.x] != 0 : m.x == 0) v = lpr[m.y];
+            if (WT && start && v != NEG_INF) v += fw[m.x];
         }
         row[c] = v;
     }
@@ -291,8 +337,12 @@ __device__ __forceinline__ void g_first_row(const GView& g, float* __restrict__ 
 
 // One frame of the recursion: row `nxt` from row `cur`, the frame's class log-probabilities read from lp_row (global) into lpr (LDS)
 // on the way.  bp_row (max pass): where each cell came from.  Ends with a barrier: nxt, and lpr, are complete.
-template <bool BEST>
-__device__ __forceinline__ void g_step(const GView& g, const float* __restrict__ cur, float* __restrict__ nxt, float* __restrict__ pre,
+// WT: aw[a] is paid when arc cell a is LEFT - every scan entry and every max candidate that comes out of an arc cell is A[a] + aw[a],
+// nothing else changes - so a row holds the cells WITHOUT their own arc's weight (the end and the occupancy add it).  In exact
+// arithmetic that is the header's "paid on entry" with every arc cell shifted by its own constant: the same ln Z, the same maxima, the
+// same candidates in the same order.  The mirrored sweep runs the same code: leaving a mirrored arc is leaving the original one too.
+template <bool BEST, bool WT>
+__device__ __forceinline__ void g_step(const GView& g, const float* __restrict__ aw, const float* __restrict__ cur, float* __restrict__ nxt, float* __restrict__ pre,
                                        float* __restrict__ suf, float* __restrict__ lpr, const float* __restrict__ lp_row, int V,
                                        int32_t* __restrict__ bp_row, int tid, int NT, int lane, int wave) {
     const int S = g.S, N = g.N;
@@ -302,11 +352,11 @@ __device__ __forceinline__ void g_step(const GView& g, const float* __restrict__
     for (int s = tid; s < S; s += NT) {
         const int2 io = g.st[s];
         const int D = io.y - io.x;
-        if (D > 0 && D < WAVE_DEG) lane_scan<BEST>(A, pre, suf, io.x, io.y);
+        if (D > 0 && D < WAVE_DEG) lane_scan<BEST, WT>(A, aw, pre, suf, io.x, io.y);
     }
     for (int kb = wave; kb < g.nbig; kb += NT >> 6) {              // the states of many incoming arcs, dealt out to the waves
         const int2 io = g.st[g.bigs[kb]];
-        wave_scan<BEST>(A, pre, suf, __builtin_amdgcn_readfirstlane(io.x), __builtin_amdgcn_readfirstlane(io.y), lane);
+        wave_scan<BEST, WT>(A, aw, pre, suf, __builtin_amdgcn_readfirstlane(io.x), __builtin_amdgcn_readfirstlane(io.y), lane);
     }
     if (tid < V) lpr[tid] = next_lp;
     __syncthreads();
@@ -317,7 +367,7 @@ __device__ __forceinline__ void g_step(const GView& g, const float* __restrict__
         if (c < S) {
             const int2 io = g.st[c];
             int arc;
-            const float inc = g_read<BEST>(suf, io.y > io.x ? io.x : -1, A, arc);
+            const float inc = g_read<BEST, WT>(suf, io.y > io.x ? io.x : -1, A, aw, arc);
             const float w = cur[c];
             if (BEST) {
                 v = w;
@@ -330,7 +380,7 @@ __device__ __forceinline__ void g_step(const GView& g, const float* __restrict__
             const int4 m = g.meta[c - S];
             int arc_a, arc_b;
             const float self = cur[c], w = cur[m.x];
-            const float pa = g_read<BEST>(pre, m.z, A, arc_a), pb = g_read<BEST>(suf, m.w, A, arc_b);
+            const float pa = g_read<BEST, WT>(pre, m.z, A, aw, arc_a), pb = g_read<BEST, WT>(suf, m.w, A, aw, arc_b);
             if (BEST) {
                 v = self;
                 if (w > v) { v = w; from = m.x; }
@@ -350,17 +400,22 @@ __device__ __forceinline__ void g_step(const GView& g, const float* __restrict__
 
 // The end: the accepting W cells in state order, then the arc cells with an accepting destination in arc order, joined over the
 // workgroup in r_m / r_s / r_i [NT]; the result is their entry 0 (after the last barrier).  len = 0: the start state's flag.
-template <bool BEST>
-__device__ __forceinline__ void g_finish(const GView& g, const float* __restrict__ cur, int len, const int32_t* __restrict__ acc_s,
+// WT: an accepting W cell adds its state's final weight fw, an arc cell its own arc's weight (it is left here) and fw of its destination.
+template <bool BEST, bool WT>
+__device__ __forceinline__ void g_finish(const GView& g, const float* __restrict__ aw, const float* __restrict__ fw,
+                                         const float* __restrict__ cur, int len, const int32_t* __restrict__ acc_s,
                                          const int32_t* __restrict__ dst, float* r_m, float* r_s, int* r_i, int tid, int NT) {
     GAcc acc = g_none();
     if (len > 0) {
         for (int c = tid; c < g.N; c += NT) {
             const bool fin = c < g.S ? acc_s[c] != 0 : acc_s[dst[c - g.S]] != 0;
-            if (fin) acc = g_join<BEST>(acc, g_elem(cur[c], c));
+            if (!fin) continue;
+            float v = cur[c];
+            if (WT) v = c < g.S ? v + fw[c] : (v + aw[c - g.S]) + fw[dst[c - g.S]];
+            acc = g_join<BEST>(acc, g_elem(v, c));
         }
     } else if (tid == 0 && acc_s[0] != 0) {
-        acc = g_elem(0.f, 0);
+        acc = g_elem(WT ? fw[0] : 0.f, 0);
     }
     r_m[tid] = acc.m;
     r_s[tid] = acc.s;
@@ -382,7 +437,7 @@ __device__ __forceinline__ void g_finish(const GView& g, const float* __restrict
 
 // grid.x = B * G, NT_SMALL or NT_BIG threads, dynamic LDS: two rows of maxN cells (states, then arcs), the two scans (maxN words
 // each, only E used) and two staged rows of class log-probabilities.  out: out_logp (sum pass) or out_best (max pass).
-template <bool BEST>
+template <bool BEST, bool WT>
 __global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __restrict__ clp, const int32_t* __restrict__ lens,
                                                              const int32_t* __restrict__ g_state_off, const int32_t* __restrict__ g_arc_off,
                                                              const int32_t* __restrict__ arc_dst, const int32_t* __restrict__ accept,
@@ -391,7 +446,7 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __rest
                                                              int stage, int T, int B, int V, int G, int max_states, int max_arcs,
                                                              float* __restrict__ out, int32_t* __restrict__ bp_all,
                                                              int32_t* __restrict__ out_labels, int32_t* __restrict__ out_lens,
-                                                             int label_stride) {
+                                                             int label_stride, GWeights<WT> GW) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float r_m[NT_BIG];
     __shared__ float r_s[NT_BIG];
@@ -415,6 +470,12 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __rest
     const int32_t* dst = arc_dst + g_arc_off[k];
     const int len = min(max(lens[b], 0), T);
     GView gv = g_view(k, S, E, st_all, meta_all, big_all, max_states, max_arcs);
+    const float* aw = nullptr;                                     // WT: the automaton's arc weights, its states' final weights
+    const float* fw = nullptr;
+    if constexpr (WT) {
+        aw = g_stage_weights(GW.arc + g_arc_off[k], E, stage, sm + 4 * maxN + 2 * VMAX, max_states, max_arcs, tid, NT);
+        fw = GW.fin + g_state_off[k];
+    }
     if (stage) gv = g_stage(gv, sm + 4 * maxN + 2 * VMAX, max_states, max_arcs, tid, NT);   // every frame reads all of the plan
     const int4* meta = gv.meta;
     float* row0 = sm;
@@ -429,18 +490,18 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_kernel(const float* __rest
     if (len > 0) {
         if (tid < V) lprow[tid] = lpb[tid];
         __syncthreads();
-        g_first_row(gv, row0, lprow, nullptr, tid, NT);
+        g_first_row<WT>(gv, row0, lprow, nullptr, fw, tid, NT);
     }
     float* cur = row0;
     float* nxt = row1;
     for (int t = 1; t < len; ++t) {
-        g_step<BEST>(gv, cur, nxt, pre, suf, lprow + (t & 1) * VMAX, lpb + t * tstride, V, BEST ? bp + (long)t * N : nullptr, tid, NT, lane,
-                     wave);
+        g_step<BEST, WT>(gv, aw, cur, nxt, pre, suf, lprow + (t & 1) * VMAX, lpb + t * tstride, V, BEST ? bp + (long)t * N : nullptr, tid,
+                         NT, lane, wave);
         float* sw = cur;
         cur = nxt;
         nxt = sw;
     }
-    g_finish<BEST>(gv, cur, len, acc_s, dst, r_m, r_s, r_i, tid, NT);
+    g_finish<BEST, WT>(gv, aw, fw, cur, len, acc_s, dst, r_m, r_s, r_i, tid, NT);
     if (!BEST) {
         if (tid == 0) out[blk] = g_value({r_m[0], r_s[0], -1});
         return;
@@ -477,12 +538,12 @@ struct Plan {
     size_t flags_bytes, st_bytes, meta_bytes, big_bytes, bp_bytes;
     int threads;
     size_t lds;
-    int stage;             // the automaton's plan is copied into LDS (it fits beside the rows)
+    int stage;             // 1: the automaton's plan is copied into LDS (it fits beside the rows); | 2: its arc weights too
     bool ok;
     size_t plan_bytes() const { return flags_bytes + st_bytes + meta_bytes + big_bytes; }
 };
 
-Plan plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want_best) {
+Plan plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want_best, bool weighted = false) {
     Plan p = {0, 0, 0, 0, 0, 0, 0, 0, false};
     if (t <= 0 || b <= 0 || v <= 1 || v > VMAX || g < 1 || max_states < 1 || max_arcs < 0) return p;
     if ((long)max_states + max_arcs > GN_MAX || (long)t * b * g >= (1L << 31)) return p;
@@ -498,10 +559,15 @@ Plan plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want
     }
     p.threads = n > N_SMALL ? NT_BIG : NT_SMALL;
     p.lds = (4 * n + 2 * VMAX) * sizeof(float);
-    const size_t staged = align16((size_t)max_arcs * sizeof(int4) + (size_t)max_states * sizeof(int2) + (size_t)big_stride(max_arcs) * sizeof(int32_t));
+    const size_t staged = staged_plan_bytes(max_states, max_arcs);
     if (p.lds + staged <= LDS_DYN_MAX) {
         p.stage = 1;
         p.lds += staged;
+        const size_t staged_w = align16((size_t)max_arcs * sizeof(float));
+        if (weighted && max_arcs > 0 && p.lds + staged_w <= LDS_DYN_MAX) {
+            p.stage = 3;
+            p.lds += staged_w;
+        }
     }
     p.ok = true;
     return p;
@@ -515,12 +581,22 @@ extern "C" size_t vocr_ctc_grammar_workspace_bytes(int t, int b, int v, int g, i
     return clp_bytes(t, b, v) + p.plan_bytes() + p.bp_bytes;
 }
 
-extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
-                                       const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
-                                       const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, int max_states, int max_arcs,
-                                       float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "vocr_ctc_grammar_scores";
+namespace {
+
+// both weight tables or neither, under the entry's name
+int check_weight_tables(const char* who, const float* arc_logw, const float* final_logw) {
+    VOCR_CHECK_ARG(!arc_logw == !final_logw, "%s: arc_logw and final_logw go together (arc_logw %s, final_logw %s)", who,
+                   arc_logw ? "given" : "NULL", final_logw ? "given" : "NULL");
+    return VOCR_OK;
+}
+
+// what vocr_ctc_grammar_scores and vocr_ctc_grammar_scores_weighted do: WT = false is the code the unweighted entry always ran
+template <bool WT>
+int grammar_scores(const char* who, const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                   const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src, const int32_t* arc_cls,
+                   const int32_t* arc_dst, const int32_t* accept, GWeights<WT> GW, int max_states, int max_arcs, float* out_logp,
+                   float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride, void* workspace, size_t workspace_bytes,
+                   void* stream) {
     VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "%s: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", who, VMAX, t, b, v);
     VOCR_CHECK_ARG(g >= 1, "%s: need g >= 1 (g=%d)", who, g);
     VOCR_CHECK_ARG(max_states >= 1 && max_arcs >= 0 && (long)max_states + max_arcs <= GN_MAX,
@@ -529,7 +605,7 @@ extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens,
     const bool any_best = out_best || out_labels || out_lens, all_best = out_best && out_labels && out_lens;
     VOCR_CHECK_ARG(any_best == all_best, "%s: out_best, out_labels and out_lens must be all NULL or all given", who);
     VOCR_CHECK_ARG(!all_best || label_stride >= t, "%s: need label_stride >= t (label_stride=%d t=%d)", who, label_stride, t);
-    const Plan p = plan_for(t, b, v, g, max_states, max_arcs, all_best ? 1 : 0);
+    const Plan p = plan_for(t, b, v, g, max_states, max_arcs, all_best ? 1 : 0, WT);
     VOCR_CHECK_ARG(p.ok, "%s: unsupported shape (t=%d b=%d v=%d g=%d max_states=%d max_arcs=%d): t*b*g must stay below 2^31 and the back "
                    "pointers, t*b*g*(max_states+max_arcs)*4 bytes, within 2 GiB", who, t, b, v, g, max_states, max_arcs);
     VOCR_CHECK_ARG(logits && lens && g_state_off && g_arc_off && accept && out_logp && workspace && (max_arcs == 0 || (arc_src && arc_cls && arc_dst)),
@@ -539,7 +615,7 @@ extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens,
     VOCR_CHECK_ARG((((uintptr_t)workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_grammar_kernel<false>, (const void*)ctc_grammar_kernel<true>};
+    const void* const big[] = {(const void*)ctc_grammar_kernel<false, WT>, (const void*)ctc_grammar_kernel<true, WT>};
     if (vocr_allow_dynamic_lds(big, 2, (int)LDS_DYN_MAX, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     char* ws = (char*)workspace;
     float* clp = (float*)ws;
@@ -549,18 +625,55 @@ extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens,
     int32_t* bigs = (int32_t*)((char*)meta + p.meta_bytes);
     int32_t* bp = (int32_t*)((char*)bigs + p.big_bytes);
     if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
-    grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, 0, flags, st,
-                                          meta, bigs);
-    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(plan)");
-    ctc_grammar_kernel<false><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs, p.stage, t, b,
-                                                             v, g, max_states, max_arcs, out_logp, nullptr, nullptr, nullptr, 0);
-    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(sum)");
+    grammar_plan_kernel<WT><<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, 0, flags,
+                                              st, meta, bigs, GW);
+    VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_scores_weighted(plan)" : "vocr_ctc_grammar_scores(plan)");
+    ctc_grammar_kernel<false, WT><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs,
+                                                                 p.stage, t, b, v, g, max_states, max_arcs, out_logp, nullptr, nullptr,
+                                                                 nullptr, 0, GW);
+    VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_scores_weighted(sum)" : "vocr_ctc_grammar_scores(sum)");
     if (all_best) {
-        ctc_grammar_kernel<true><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta, bigs, p.stage, t,
-                                                                b, v, g, max_states, max_arcs, out_best, bp, out_labels, out_lens, label_stride);
-        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_scores(max)");
+        ctc_grammar_kernel<true, WT><<<b * g, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, flags, st, meta,
+                                                                    bigs, p.stage, t, b, v, g, max_states, max_arcs, out_best, bp,
+                                                                    out_labels, out_lens, label_stride, GW);
+        VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_scores_weighted(max)" : "vocr_ctc_grammar_scores(max)");
     }
     return VOCR_OK;
+}
+
+}  // namespace
+
+extern "C" int vocr_ctc_grammar_scores(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                       const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
+                                       const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, int max_states, int max_arcs,
+                                       float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens, int label_stride,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    return grammar_scores<false>("vocr_ctc_grammar_scores", logits, lens, t, b, v, canon, g_state_off, g_arc_off, g, arc_src, arc_cls,
+                                 arc_dst, accept, {}, max_states, max_arcs, out_logp, out_best, out_labels, out_lens, label_stride,
+                                 workspace, workspace_bytes, stream);
+}
+
+// The same with weights on the arcs and on the accepting states (the header above; "paid on leaving": g_step).  The workspace is the
+// unweighted entry's: the weights are read where the caller keeps them, or staged in LDS.
+extern "C" size_t vocr_ctc_grammar_weighted_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_best) {
+    return vocr_ctc_grammar_workspace_bytes(t, b, v, g, max_states, max_arcs, want_best);
+}
+
+extern "C" int vocr_ctc_grammar_scores_weighted(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                                const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
+                                                const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept,
+                                                const float* arc_logw, const float* final_logw, int max_states, int max_arcs,
+                                                float* out_logp, float* out_best, int32_t* out_labels, int32_t* out_lens,
+                                                int label_stride, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "vocr_ctc_grammar_scores_weighted";
+    if (const int rc = check_weight_tables(who, arc_logw, final_logw)) return rc;
+    if (!arc_logw)
+        return grammar_scores<false>(who, logits, lens, t, b, v, canon, g_state_off, g_arc_off, g, arc_src, arc_cls, arc_dst, accept, {},
+                                     max_states, max_arcs, out_logp, out_best, out_labels, out_lens, label_stride, workspace,
+                                     workspace_bytes, stream);
+    return grammar_scores<true>(who, logits, lens, t, b, v, canon, g_state_off, g_arc_off, g, arc_src, arc_cls, arc_dst, accept,
+                                {arc_logw, final_logw, accept}, max_states, max_arcs, out_logp, out_best, out_labels, out_lens,
+                                label_stride, workspace, workspace_bytes, stream);
 }
 
 // ---- vocr_ctc_grammar_grad: ln P of line b under automaton which[b], and its gradient with respect to the logits ----
@@ -605,13 +718,16 @@ __device__ __forceinline__ void g_sort(unsigned long long* keys, int p2, int tid
 }
 
 // grid.x = G.  Nothing is written for an automaton whose offsets break a rule (the plan kernel flags it from the same test); one
-// that breaks another rule gets tables that stay within bounds and are never swept.
+// that breaks another rule gets tables that stay within bounds and are never swept.  WT: m_logw[r] = the weight of the arc behind
+// mirrored arc r - the weights are permuted with the arcs.
+template <bool WT>
 __global__ __launch_bounds__(NT_BIG) void grammar_mirror_kernel(const int32_t* __restrict__ canon, const int32_t* __restrict__ g_state_off,
                                                                 const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_src,
                                                                 const int32_t* __restrict__ arc_cls, const int32_t* __restrict__ arc_dst,
                                                                 int V, int max_states, int max_arcs, int p2max,
                                                                 unsigned long long* keys_all, int32_t* m_src, int32_t* m_cls,
-                                                                int32_t* m_dst, int32_t* perm_all, int32_t* cpos_all, int32_t* cbeg_all) {
+                                                                int32_t* m_dst, int32_t* perm_all, int32_t* cpos_all, int32_t* cbeg_all,
+                                                                GWeights<WT> GW, float* m_logw) {
     const int k = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
     const int s0 = g_state_off[k], a0 = g_arc_off[k];
     const long S_ = (long)g_state_off[k + 1] - s0, E_ = (long)g_arc_off[k + 1] - a0;
@@ -646,6 +762,7 @@ __global__ __launch_bounds__(NT_BIG) void grammar_mirror_kernel(const int32_t* _
         mc[r] = cls[i];
         md[r] = src[i];
         perm[r] = i;
+        if constexpr (WT) m_logw[(long)k * max_arcs + r] = GW.arc[a0 + i];
     }
     __syncthreads();
     for (int r = tid; r < p2; r += NT) {
@@ -671,13 +788,15 @@ __device__ __forceinline__ void g_zero_rows(float* __restrict__ dlogits, int b, 
 
 // grid.x = B, NT_SMALL or NT_BIG threads, ctc_grammar_kernel's dynamic LDS.  dlogits = NULL: scores only (lat and the mirrored
 // plan are not touched); else the rows of a line with a score hold occ(t, k) behind it, every other row zeros.
+template <bool WT>
 __global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
     const float* __restrict__ clp, const int32_t* __restrict__ lens, const int32_t* __restrict__ g_state_off, const int32_t* __restrict__ g_arc_off, const int32_t* __restrict__ arc_dst,
     const int32_t* __restrict__ accept, const int32_t* __restrict__ which,
     const int32_t* __restrict__ flags_f, const int2* __restrict__ st_f, const int4* __restrict__ meta_f, const int32_t* __restrict__ big_f,
     const int32_t* __restrict__ flags_m, const int2* __restrict__ st_m, const int4* __restrict__ meta_m, const int32_t* __restrict__ big_m,
     const int32_t* __restrict__ perm_all, const int32_t* __restrict__ cpos_all, const int32_t* __restrict__ cbeg_all, int stage, int T,
-    int B, int V, int G, int max_states, int max_arcs, float* __restrict__ out_logp, float* __restrict__ lat, float* __restrict__ dlogits) {
+    int B, int V, int G, int max_states, int max_arcs, float* __restrict__ out_logp, float* __restrict__ lat, float* __restrict__ dlogits,
+    GWeights<WT> GW, const float* __restrict__ m_logw) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float r_m[NT_BIG];
     __shared__ float r_s[NT_BIG];
@@ -699,6 +818,12 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
     const int len = min(max(lens[b], 0), T);
     float* stage_at = sm + 4 * maxN + 2 * VMAX;
     GView gv = g_view(k, S, E, st_f, meta_f, big_f, max_states, max_arcs);
+    const float* aw = nullptr;                                     // WT: the arc weights of the sweep at hand, the states' final weights
+    const float* fw = nullptr;
+    if constexpr (WT) {
+        aw = g_stage_weights(GW.arc + g_arc_off[k], E, stage, stage_at, max_states, max_arcs, tid, NT);
+        fw = GW.fin + g_state_off[k];
+    }
     if (stage) gv = g_stage(gv, stage_at, max_states, max_arcs, tid, NT);
     float* row0 = sm;
     float* row1 = sm + maxN;
@@ -713,21 +838,21 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
     if (len > 0) {
         if (tid < V) lprow[tid] = lpb[tid];
         __syncthreads();
-        g_first_row(gv, row0, lprow, nullptr, tid, NT);
+        g_first_row<WT>(gv, row0, lprow, nullptr, fw, tid, NT);
         if (lat_b)
             for (int c = tid; c < N; c += NT) lat_b[c] = row0[c];
     }
     float* cur = row0;
     float* nxt = row1;
     for (int t = 1; t < len; ++t) {
-        g_step<false>(gv, cur, nxt, pre, suf, lprow + (t & 1) * VMAX, lpb + t * tstride, V, nullptr, tid, NT, lane, wave);
+        g_step<false, WT>(gv, aw, cur, nxt, pre, suf, lprow + (t & 1) * VMAX, lpb + t * tstride, V, nullptr, tid, NT, lane, wave);
         float* sw = cur;
         cur = nxt;
         nxt = sw;
         if (lat_b)
             for (int c = tid; c < N; c += NT) lat_b[(long)t * maxN + c] = cur[c];
     }
-    g_finish<false>(gv, cur, len, acc_s, dst, r_m, r_s, r_i, tid, NT);
+    g_finish<false, WT>(gv, aw, fw, cur, len, acc_s, dst, r_m, r_s, r_i, tid, NT);
     const float lnP = g_value({r_m[0], r_s[0], -1});
     if (tid == 0) out_logp[b] = lnP;
     if (!dlogits) return;
@@ -744,27 +869,34 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
     // Nothing in the frame loop waits for global memory: what a thread needs of its cells c = tid + i NT (at most CPT of them:
     // N <= CPT * NT at both thread counts) is in registers before it starts, and the forward row of frame t is loaded ahead of
     // the step that makes frame t's bhat.
+    // WT: alpha and bhat of an arc cell both leave its own weight out (it is paid on leaving, in either direction), every other weight
+    // of a path through the cell is in exactly one of them - the earlier arcs' in alpha, the later arcs' and the final weight (the
+    // mirrored sweep's start weight) in bhat - so the occupancy adds the cell's own weight, once.
     gv = g_view(k, S, E, st_m, meta_m, big_m, max_states, max_arcs);
+    if constexpr (WT) aw = g_stage_weights(m_logw + (long)k * max_arcs, E, stage, stage_at, max_states, max_arcs, tid, NT);
     if (stage) gv = g_stage(gv, stage_at, max_states, max_arcs, tid, NT);
     const int32_t* perm = perm_all + (long)k * max_arcs;
     const int32_t* cpos = cpos_all + (long)k * max_arcs;
     int ai[CPT], zi[CPT], ecol[CPT];                               // the cell's word in a forward row, its slot among the class-sorted z, its class
+    float wz[WT ? CPT : 1];                                        // WT: the cell's own arc weight (0 for a W cell)
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
         const int c = tid + i * NT;
         ai[i] = -1;
         zi[i] = ecol[i] = 0;
+        if constexpr (WT) wz[i] = 0.f;
         if (c < S) {
             ai[i] = zi[i] = c;
         } else if (c < N) {
             ai[i] = S + perm[c - S];
             zi[i] = S + cpos[c - S];
             ecol[i] = gv.meta[c - S].y;
+            if constexpr (WT) wz[i] = aw[c - S];
         }
     }
     if (tid < V) lprow[tid] = lpb[(long)(len - 1) * tstride + tid];
     __syncthreads();
-    g_first_row(gv, row0, lprow, acc_s, tid, NT);
+    g_first_row<WT>(gv, row0, lprow, acc_s, fw, tid, NT);
     cur = row0;
     nxt = row1;
     for (int j = 0; j < len; ++j) {
@@ -775,7 +907,7 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
 #pragma unroll
         for (int i = 0; i < CPT; ++i) a[i] = ai[i] >= 0 ? al[ai[i]] : NEG_INF;
         if (j > 0) {
-            g_step<false>(gv, cur, nxt, pre, suf, lprow + (j & 1) * VMAX, lpb + t * tstride, V, nullptr, tid, NT, lane, wave);
+            g_step<false, WT>(gv, aw, cur, nxt, pre, suf, lprow + (j & 1) * VMAX, lpb + t * tstride, V, nullptr, tid, NT, lane, wave);
             float* sw = cur;
             cur = nxt;
             nxt = sw;
@@ -784,7 +916,9 @@ __global__ __launch_bounds__(NT_BIG) void ctc_grammar_grad_kernel(
         for (int i = 0; i < CPT; ++i) {                            // z(c): the share of the accepted mass that passes through c at t
             if (ai[i] < 0) continue;
             const float bh = cur[tid + i * NT];
-            pre[zi[i]] = (a[i] == NEG_INF || bh == NEG_INF) ? 0.f : expf(a[i] + bh - lpr[ecol[i]] - lnP);
+            float ab = a[i] + bh;
+            if constexpr (WT) ab += wz[i];
+            pre[zi[i]] = (a[i] == NEG_INF || bh == NEG_INF) ? 0.f : expf(ab - lpr[ecol[i]] - lnP);
         }
         __syncthreads();
         float* occ_row = dlogits + ((long)t * B + b) * V;          // occ(t, k) waits here for the row kernel
@@ -835,8 +969,8 @@ struct GradPlan {
     size_t mirror_bytes() const { return 5 * arcs_bytes + keys_bytes + cbeg_bytes + p.plan_bytes(); }
 };
 
-GradPlan grad_plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad) {
-    GradPlan q = {plan_for(t, b, v, g, max_states, max_arcs, 0), 1, 0, 0, 0, 0, false};
+GradPlan grad_plan_for(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad, bool weighted = false) {
+    GradPlan q = {plan_for(t, b, v, g, max_states, max_arcs, 0, weighted), 1, 0, 0, 0, 0, false};
     if (!q.p.ok) return q;
     q.ok = true;
     if (!want_grad) return q;
@@ -850,20 +984,35 @@ GradPlan grad_plan_for(int t, int b, int v, int g, int max_states, int max_arcs,
     return q;
 }
 
+// what both gradient entries need; the weighted entry (weighted_entry) keeps the mirrored weights behind everything else
+size_t grad_need(const GradPlan& q, int t, int b, int v, int want_grad, bool weighted_entry) {
+    return clp_bytes(t, b, v) + q.p.plan_bytes() + (want_grad ? q.mirror_bytes() + q.lattice_bytes + (weighted_entry ? q.arcs_bytes : 0) : 0);
+}
+
 }  // namespace
 
 extern "C" size_t vocr_ctc_grammar_grad_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad) {
     const GradPlan q = grad_plan_for(t, b, v, g, max_states, max_arcs, want_grad);
     if (!q.ok) return 0;
-    return clp_bytes(t, b, v) + q.p.plan_bytes() + (want_grad ? q.mirror_bytes() + q.lattice_bytes : 0);
+    return grad_need(q, t, b, v, want_grad, false);
 }
 
-extern "C" int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
-                                     const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
-                                     const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, int max_states, int max_arcs,
-                                     const int32_t* which, const float* weights, float* out_logp, float* dlogits, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    const char* who = "vocr_ctc_grammar_grad";
+// the weighted entry's: one more float per arc slot, the mirrored weights
+extern "C" size_t vocr_ctc_grammar_grad_weighted_workspace_bytes(int t, int b, int v, int g, int max_states, int max_arcs, int want_grad) {
+    const GradPlan q = grad_plan_for(t, b, v, g, max_states, max_arcs, want_grad);
+    if (!q.ok) return 0;
+    return grad_need(q, t, b, v, want_grad, true);
+}
+
+namespace {
+
+// what vocr_ctc_grammar_grad and vocr_ctc_grammar_grad_weighted do: WT = false is the code the unweighted entry always ran, in the
+// same workspace layout (weighted_entry only asks for the mirrored weights' room behind it)
+template <bool WT>
+int grammar_grad(const char* who, bool weighted_entry, const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                 const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src, const int32_t* arc_cls,
+                 const int32_t* arc_dst, const int32_t* accept, GWeights<WT> GW, int max_states, int max_arcs, const int32_t* which,
+                 const float* weights, float* out_logp, float* dlogits, void* workspace, size_t workspace_bytes, void* stream) {
     VOCR_CHECK_ARG(t > 0 && b > 0 && v > 1 && v <= VMAX, "%s: need t > 0, b > 0, 2 <= v <= %d (t=%d b=%d v=%d)", who, VMAX, t, b, v);
     VOCR_CHECK_ARG(g >= 1, "%s: need g >= 1 (g=%d)", who, g);
     VOCR_CHECK_ARG(max_states >= 1 && max_arcs >= 0 && (long)max_states + max_arcs <= GN_MAX,
@@ -872,17 +1021,17 @@ extern "C" int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, i
     VOCR_CHECK_ARG(!weights == !dlogits, "%s: weights and dlogits go together (weights %s, dlogits %s)", who, weights ? "given" : "NULL",
                    dlogits ? "given" : "NULL");
     const int want_grad = dlogits ? 1 : 0;
-    const GradPlan q = grad_plan_for(t, b, v, g, max_states, max_arcs, want_grad);
+    const GradPlan q = grad_plan_for(t, b, v, g, max_states, max_arcs, want_grad, WT);
     VOCR_CHECK_ARG(q.ok, "%s: unsupported shape (t=%d b=%d v=%d g=%d max_states=%d max_arcs=%d): t*b*g must stay below 2^31 and the stored "
                    "lattice, t*b*(max_states+max_arcs)*4 bytes, within 2 GiB", who, t, b, v, g, max_states, max_arcs);
     VOCR_CHECK_ARG(logits && lens && g_state_off && g_arc_off && accept && which && out_logp && workspace &&
                    (max_arcs == 0 || (arc_src && arc_cls && arc_dst)), "%s: null pointer", who);
-    const size_t need = clp_bytes(t, b, v) + q.p.plan_bytes() + (want_grad ? q.mirror_bytes() + q.lattice_bytes : 0);
+    const size_t need = grad_need(q, t, b, v, want_grad, weighted_entry);
     VOCR_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     VOCR_CHECK_ARG((((uintptr_t)workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     static VocrPerDevice lds_set;
-    const void* const big[] = {(const void*)ctc_grammar_grad_kernel};
+    const void* const big[] = {(const void*)ctc_grammar_grad_kernel<WT>};
     if (vocr_allow_dynamic_lds(big, 1, (int)LDS_DYN_MAX, &lds_set, who) != VOCR_OK) return VOCR_ELAUNCH;
     const Plan& p = q.p;
     char* at = (char*)workspace;
@@ -897,13 +1046,14 @@ extern "C" int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, i
     int4* meta = (int4*)take(p.meta_bytes);
     int32_t* bigs = (int32_t*)take(p.big_bytes);
     if (launch_class_logprob(who, logits, lens, canon, clp, t, b, v, s) != VOCR_OK) return VOCR_ELAUNCH;
-    grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, 0, flags, st,
-                                          meta, bigs);
-    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(plan)");
+    grammar_plan_kernel<WT><<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v, max_states, max_arcs, 0, flags,
+                                              st, meta, bigs, GW);
+    VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_grad_weighted(plan)" : "vocr_ctc_grammar_grad(plan)");
     int32_t *flags_m = nullptr, *bigs_m = nullptr, *perm = nullptr, *cpos = nullptr, *cbeg = nullptr;
     int2* st_m = nullptr;
     int4* meta_m = nullptr;
     float* lat = nullptr;
+    float* m_logw = nullptr;
     if (want_grad) {
         flags_m = (int32_t*)take(p.flags_bytes);
         st_m = (int2*)take(p.st_bytes);
@@ -917,21 +1067,51 @@ extern "C" int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, i
         cpos = (int32_t*)take(q.arcs_bytes);
         cbeg = (int32_t*)take(q.cbeg_bytes);
         lat = (float*)take(q.lattice_bytes);
-        grammar_mirror_kernel<<<g, max_arcs > 1024 ? NT_BIG : NT_SMALL, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst, v,
-                                                                               max_states, max_arcs, q.p2, keys, m_src, m_cls, m_dst, perm,
-                                                                               cpos, cbeg);
-        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(mirror)");
-        grammar_plan_kernel<<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, m_src, m_cls, m_dst, v, max_states, max_arcs,
-                                              max_arcs > 0 ? max_arcs : 1, flags_m, st_m, meta_m, bigs_m);
-        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(mirrored plan)");
+        if (WT) m_logw = (float*)take(q.arcs_bytes);
+        grammar_mirror_kernel<WT><<<g, max_arcs > 1024 ? NT_BIG : NT_SMALL, 0, s>>>(canon, g_state_off, g_arc_off, arc_src, arc_cls, arc_dst,
+                                                                                   v, max_states, max_arcs, q.p2, keys, m_src, m_cls, m_dst,
+                                                                                   perm, cpos, cbeg, GW, m_logw);
+        VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_grad_weighted(mirror)" : "vocr_ctc_grammar_grad(mirror)");
+        // (the forward plan has judged the weights: the mirrored plan checks the arcs alone)
+        grammar_plan_kernel<false><<<g, 256, 0, s>>>(canon, g_state_off, g_arc_off, m_src, m_cls, m_dst, v, max_states, max_arcs,
+                                                     max_arcs > 0 ? max_arcs : 1, flags_m, st_m, meta_m, bigs_m, {});
+        VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_grad_weighted(mirrored plan)" : "vocr_ctc_grammar_grad(mirrored plan)");
     }
-    ctc_grammar_grad_kernel<<<b, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, which, flags, st, meta, bigs, flags_m,
-                                                        st_m, meta_m, bigs_m, perm, cpos, cbeg, p.stage, t, b, v, g, max_states, max_arcs,
-                                                        out_logp, lat, dlogits);
-    VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(sweep)");
+    ctc_grammar_grad_kernel<WT><<<b, p.threads, p.lds, s>>>(clp, lens, g_state_off, g_arc_off, arc_dst, accept, which, flags, st, meta, bigs,
+                                                            flags_m, st_m, meta_m, bigs_m, perm, cpos, cbeg, p.stage, t, b, v, g, max_states,
+                                                            max_arcs, out_logp, lat, dlogits, GW, m_logw);
+    VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_grad_weighted(sweep)" : "vocr_ctc_grammar_grad(sweep)");
     if (want_grad) {
         grammar_grad_rows_kernel<<<vocr_cdiv((long)t * b, 4), 256, 0, s>>>(logits, clp, lens, canon, weights, out_logp, t, b, v, dlogits);
-        VOCR_CHECK_LAUNCH("vocr_ctc_grammar_grad(rows)");
+        VOCR_CHECK_LAUNCH(WT ? "vocr_ctc_grammar_grad_weighted(rows)" : "vocr_ctc_grammar_grad(rows)");
     }
     return VOCR_OK;
+}
+
+}  // namespace
+
+extern "C" int vocr_ctc_grammar_grad(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                     const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
+                                     const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, int max_states, int max_arcs,
+                                     const int32_t* which, const float* weights, float* out_logp, float* dlogits, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return grammar_grad<false>("vocr_ctc_grammar_grad", false, logits, lens, t, b, v, canon, g_state_off, g_arc_off, g, arc_src, arc_cls,
+                               arc_dst, accept, {}, max_states, max_arcs, which, weights, out_logp, dlogits, workspace, workspace_bytes,
+                               stream);
+}
+
+extern "C" int vocr_ctc_grammar_grad_weighted(const float* logits, const int32_t* lens, int t, int b, int v, const int32_t* canon,
+                                              const int32_t* g_state_off, const int32_t* g_arc_off, int g, const int32_t* arc_src,
+                                              const int32_t* arc_cls, const int32_t* arc_dst, const int32_t* accept, const float* arc_logw,
+                                              const float* final_logw, int max_states, int max_arcs, const int32_t* which,
+                                              const float* weights, float* out_logp, float* dlogits, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+    const char* who = "vocr_ctc_grammar_grad_weighted";
+    if (const int rc = check_weight_tables(who, arc_logw, final_logw)) return rc;
+    if (!arc_logw)
+        return grammar_grad<false>(who, true, logits, lens, t, b, v, canon, g_state_off, g_arc_off, g, arc_src, arc_cls, arc_dst, accept, {},
+                                   max_states, max_arcs, which, weights, out_logp, dlogits, workspace, workspace_bytes, stream);
+    return grammar_grad<true>(who, true, logits, lens, t, b, v, canon, g_state_off, g_arc_off, g, arc_src, arc_cls, arc_dst, accept,
+                              {arc_logw, final_logw, accept}, max_states, max_arcs, which, weights, out_logp, dlogits, workspace,
+                              workspace_bytes, stream);
 }

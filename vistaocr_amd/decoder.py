@@ -185,11 +185,13 @@ class GrammarBeamDecoder(_SearchDecoder):
     leaves the beam at once.  `grammars`: one Grammar or a list; `which=` on the public methods takes one index into the list per line
     (None: grammar 0 for every line).  A line whose language nothing in the beam reaches (or that needs more symbols than the line has
     frames) has no hypothesis: "" / None / an empty n-best list, as with the other decoders.  It is a beam search: not exact beyond
-    the beam; the automata are deterministic and carry no weights (the LM is the character n-gram).  The sweep kernels' 8192 cells do
-    not apply: the dense tables are bounded by `max_table_bytes` alone."""
+    the beam; the automata are deterministic.  WEIGHTED grammars (Grammar.boost: hot words; Grammar.from_words(log_weights=): a prior
+    over a lexicon; Grammar.from_ngram) add grammar_weight * (the weight of the labelling under its grammar) to a hypothesis's rank,
+    prefix by prefix, next to the LM term (vocr_ctc_grammar_beam_search_weighted); decode_nbest(grammar_scores=True) lists that weight
+    as a fourth score.  The sweep kernels' 8192 cells do not apply: the dense tables are bounded by `max_table_bytes` alone."""
 
     def __init__(self, alphabet, grammars, beam=16, nbest=1, lm=None, lm_weight=0.0, insertion_bonus=0.0, prune_logp=None,
-                 max_table_bytes=1 << 30):
+                 max_table_bytes=1 << 30, grammar_weight=1.0):
         super().__init__(alphabet, beam, nbest)
         if lm is not None and lm.logp.shape[1] != len(alphabet):
             raise ValueError("GrammarBeamDecoder: the LM was resolved for %d symbols, the alphabet has %d"
@@ -203,9 +205,18 @@ class GrammarBeamDecoder(_SearchDecoder):
                                  % (g.name, len(g.alphabet), len(alphabet)))
         self.lm, self.lm_weight, self.insertion_bonus, self.prune_logp = lm, float(lm_weight), float(insertion_bonus), prune_logp
         self.max_table_bytes = int(max_table_bytes)
+        self.grammar_weight = float(grammar_weight)
+        if not np.isfinite(self.grammar_weight):
+            raise ValueError("GrammarBeamDecoder: grammar_weight must be finite")
         self._packed = {}
 
-    def _search_device(self, model_output, batch_actual_timesteps, nbest, which=None):
+    def decode_nbest(self, model_output, batch_actual_timesteps, nbest=None, which=None, grammar_scores=False):
+        """_SearchDecoder.decode_nbest; with grammar_scores every hypothesis's scores are (total, acoustic, lm, grammar): the raw weight
+        of its labelling under the line's grammar (0 for an unweighted one), which total holds grammar_weight times."""
+        nbest = self.nbest if nbest is None else int(nbest)
+        return _nbest_lists(*self._search(model_output, batch_actual_timesteps, nbest, which=which, grammar_scores=grammar_scores))
+
+    def _search_device(self, model_output, batch_actual_timesteps, nbest, which=None, grammar_scores=False):
         dev = model_output.device
         canon, new = self._canon_on(dev)
         if new:
@@ -216,9 +227,12 @@ class GrammarBeamDecoder(_SearchDecoder):
                 raise ValueError("GrammarBeamDecoder: %d entries of which for %d lines" % (len(which), int(model_output.shape[1])))
             if min(which) < 0 or max(which) >= len(self.grammars):
                 raise ValueError("GrammarBeamDecoder: which must index the %d grammars" % len(self.grammars))
-        return ops.ctc_grammar_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._packed[str(dev)], which,
-                                           canon, self.beam, nbest, self.lm.to(dev) if self.lm is not None else None,
-                                           self.lm_weight, self.insertion_bonus, self.prune_logp)
+        out = ops.ctc_grammar_beam_search(model_output.detach(), _line_lengths(batch_actual_timesteps), self._packed[str(dev)], which,
+                                          canon, self.beam, nbest, self.lm.to(dev) if self.lm is not None else None,
+                                          self.lm_weight, self.insertion_bonus, self.prune_logp, self.grammar_weight, grammar_scores)
+        if not grammar_scores:
+            return out
+        return out[0], out[1], torch.cat([out[2], out[3].unsqueeze(-1)], dim=-1)      # the grammar's share as a fourth score
 
 
 def _line_lengths(batch_actual_timesteps):

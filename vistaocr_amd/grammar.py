@@ -4,7 +4,9 @@ the network's output itself.
 
 WHAT THE NUMBER IS: for a line and a grammar (a deterministic finite automaton over the alphabet's symbol classes), the probability
 under the CTC model that the line's collapsed labelling is accepted: the exact sum over ALL frame paths, no beam, no hypothesis, no
-pruning.  WHAT IT IS NOT: there are no weights on the arcs (no language model, no n-gram), and the "best" result is
+pruning.  WEIGHTED GRAMMARS (from_words(log_weights=), boost, from_ngram, from_dfa(arc_weights=, final_weights=)) carry a natural-log
+weight on every arc and every accepting state; the number is then ln Z = ln of the sum of P(path) * exp(weight of the labelling), a
+probability only when the weights normalise.  WHAT IT IS NOT: the "best" result is
 the best single PATH through the grammar (frame path and state sequence), not the most probable accepted LABELLING (which would sum the
 paths of each labelling first: decoder.GrammarBeamDecoder searches for that, over the dense tables of Grammar.dense_tables /
 pack_dense_grammars).  Characters are compared as the alphabet's symbol strings: indices with the same string are one class
@@ -353,6 +355,107 @@ def _minimize(trans, accept):
     return out_t, out_a
 
 
+def _minimize_weighted(trans, accept, tw, fw):
+    """_minimize for an automaton with weights: tw[s][c] the weight of the arc of s on class c, fw[s] the final weight of an accepting
+    state.  Trim, then partition refinement with the final weight in the initial partition and (class -> block, weight) in the
+    signature: states are merged only when they agree on every weight, so the language and the weight of every labelling are kept.
+    Correct, not claimed minimal: the weights are not pushed.  Returns (trans, accept, tw, fw)."""
+    n = len(trans)
+    reach, stack = {0}, [0]
+    while stack:
+        for d in trans[stack.pop()].values():
+            if d not in reach:
+                reach.add(d)
+                stack.append(d)
+    back = [[] for _ in range(n)]
+    for s in reach:
+        for d in trans[s].values():
+            back[d].append(s)
+    live = {s for s in reach if accept[s]}
+    stack = list(live)
+    while stack:
+        for s in back[stack.pop()]:
+            if s not in live:
+                live.add(s)
+                stack.append(s)
+    if 0 not in live:
+        return [{}], [False], [{}], [0.0]
+    keep = sorted(live)
+    first = {}
+    block = {s: first.setdefault((bool(accept[s]), float(fw[s]) if accept[s] else 0.0), len(first)) for s in keep}
+    count = len(first)
+    while True:
+        sig = {s: (block[s], tuple(sorted((c, block[d], float(tw[s][c])) for c, d in trans[s].items() if d in live))) for s in keep}
+        ids = {}
+        for s in keep:
+            ids.setdefault(sig[s], len(ids))
+        block = {s: ids[sig[s]] for s in keep}
+        if len(ids) == count:
+            break
+        count = len(ids)
+    rep = {}
+    for s in keep:
+        rep.setdefault(block[s], s)
+    number, order = {block[0]: 0}, [block[0]]
+    k = 0
+    while k < len(order):
+        s = rep[order[k]]
+        for c in sorted(trans[s]):
+            d = trans[s][c]
+            if d in live and block[d] not in number:
+                number[block[d]] = len(order)
+                order.append(block[d])
+        k += 1
+    out_t, out_a, out_w, out_f = [], [], [], []
+    for blk in order:
+        s = rep[blk]
+        out_t.append({c: number[block[d]] for c, d in trans[s].items() if d in live})
+        out_w.append({c: float(tw[s][c]) for c, d in trans[s].items() if d in live})
+        out_a.append(bool(accept[s]))
+        out_f.append(float(fw[s]) if accept[s] else 0.0)
+    return out_t, out_a, out_w, out_f
+
+
+def _check_weights(where, trans, accept, tw, fw):
+    """The rules of a weighted automaton's tables: one weight per arc, one final weight per state, every one of them finite."""
+    if len(tw) != len(trans) or len(fw) != len(trans):
+        raise ValueError("%s: need the arc weights of every state and one final weight per state (%d states, %d rows of arc weights, "
+                         "%d final weights)" % (where, len(trans), len(tw), len(fw)))
+    for s, row in enumerate(trans):
+        if set(tw[s]) != set(row):
+            raise ValueError("%s: state %d has arcs on the classes %s but weights on %s" % (where, s, sorted(row), sorted(tw[s])))
+        for c in row:
+            if not np.isfinite(float(tw[s][c])):
+                raise ValueError("%s: the weight of state %d's arc on class %d is %r: weights must be finite" % (where, s, c, tw[s][c]))
+        if accept[s] and not np.isfinite(float(fw[s])):
+            raise ValueError("%s: the final weight of state %d is %r: weights must be finite" % (where, s, fw[s]))
+
+
+def _check_trimmed(where, trans, accept):
+    """What as_given promises: every state is reached from state 0 and reaches an accepting state."""
+    n = len(trans)
+    reach, stack = {0}, [0]
+    back = [[] for _ in range(n)]
+    for s, row in enumerate(trans):
+        for d in row.values():
+            back[d].append(s)
+    while stack:
+        for d in trans[stack.pop()].values():
+            if d not in reach:
+                reach.add(d)
+                stack.append(d)
+    live = {s for s in range(n) if accept[s]}
+    stack = list(live)
+    while stack:
+        for s in back[stack.pop()]:
+            if s not in live:
+                live.add(s)
+                stack.append(s)
+    if len(reach) != n or len(live) != n:
+        raise ValueError("%s: as_given needs trimmed tables, but %d of %d states are unreachable and %d cannot reach an accepting state"
+                         % (where, n - len(reach), n, n - len(live)))
+
+
 class _Marker(object):
     def __init__(self, name):
         self.name = name
@@ -369,22 +472,49 @@ class Grammar(object):
     ANY = _Marker("ANY")                                    # from_template: exactly one arbitrary symbol
     GAP = _Marker("GAP")                                    # from_template: any string, the empty one included
 
-    def __init__(self, alphabet, trans, accept, name="grammar"):
+    def __init__(self, alphabet, trans, accept, name="grammar", arc_w=None, final_w=None, as_given=False, dense_only=False):
+        """arc_w (per state a dict class -> natural-log weight) and final_w (one per state, read for accepting states) make the grammar
+        WEIGHTED; they go together.  as_given: the tables are already trimmed (checked: a ValueError otherwise) and are kept state for
+        state, neither renumbered nor merged (from_ngram).  dense_only:
+        no arc arrays are built, only dense_tables / dense_weights (an automaton beyond the sweep kernels' cells, for the beam)."""
         self.alphabet, self.name = alphabet, name
         self._canon = alphabet.canonical_indices()
-        self._trans, acc = _minimize(trans, accept)
+        if (arc_w is None) != (final_w is None):
+            raise ValueError("Grammar: arc weights and final weights go together")
+        self.weighted = arc_w is not None
+        if self.weighted:
+            _check_weights(name, trans, accept, arc_w, final_w)
+            if as_given:
+                _check_trimmed(name, trans, accept)
+                self._trans, acc = [dict(r) for r in trans], [bool(a) for a in accept]
+                self._tw, fw = [dict(r) for r in arc_w], [float(f) if a else 0.0 for f, a in zip(final_w, accept)]
+            else:
+                self._trans, acc, self._tw, fw = _minimize_weighted(trans, accept, arc_w, final_w)
+            self._fw = np.array(fw, dtype=np.float64)
+        else:
+            self._trans, acc = _minimize(trans, accept)
+            self._tw, self._fw = None, None
         self.accept = np.array(acc, dtype=np.int32)
+        self.dense_only = bool(dense_only)
+        self._n_arcs = sum(len(row) for row in self._trans)
+        self.arc_dst = self.arc_cls = self.arc_src = self.arc_logw = self.final_logw = None
+        if self.dense_only:
+            return
         arcs = sorted((d, c, s) for s, row in enumerate(self._trans) for c, d in row.items())
         self.arc_dst = np.array([a[0] for a in arcs], dtype=np.int32)
         self.arc_cls = np.array([a[1] for a in arcs], dtype=np.int32)
         self.arc_src = np.array([a[2] for a in arcs], dtype=np.int32)
+        if self.weighted:                                   # the weights in the kernel's arc order, the final weights per state
+            self.arc_logw = np.array([self._tw[a[2]][a[1]] for a in arcs], dtype=np.float32)
+            self.final_logw = self._fw.astype(np.float32)
 
     n_states = property(lambda self: len(self._trans))
-    n_arcs = property(lambda self: int(self.arc_dst.size))
+    n_arcs = property(lambda self: self._n_arcs)
 
     @property
     def max_in_degree(self):
-        return int(np.bincount(self.arc_dst, minlength=1).max()) if self.n_arcs else 0
+        dst = [d for row in self._trans for d in row.values()]
+        return int(np.bincount(dst, minlength=1).max()) if dst else 0
 
     def dfa(self):
         """(per state a dict class -> state, accept flags): the tables from_dfa takes."""
@@ -402,6 +532,39 @@ class Grammar(object):
             if s is None:
                 return False
         return bool(self.accept[s])
+
+    def weight_of(self, labels):
+        """The total weight of a labelling (a utf-8 string or a sequence of alphabet indices) - the sum of its arcs' weights and the
+        final weight of the state it ends in, in float64 on the host - or None when the automaton rejects it.  0.0 for an accepted
+        labelling of an unweighted grammar."""
+        try:
+            seq = _labels(self.alphabet, self._canon, labels, "weight_of")
+        except ValueError:
+            return None
+        s, w = 0, 0.0
+        for c in seq:
+            n = self._trans[s].get(c)
+            if n is None:
+                return None
+            if self.weighted:
+                w += self._tw[s][c]
+            s = n
+        if not self.accept[s]:
+            return None
+        return w + float(self._fw[s]) if self.weighted else 0.0
+
+    def dense_weights(self):
+        """(logw float32 [S,V], final float32 [S]), the weight tables of the weighted grammar beam search in dense_tables' indexing:
+        logw[s, c] the weight of the arc of s on class c (0 where there is none), final[s] the final weight (0 for a state that does
+        not accept).  Zeros for an unweighted grammar."""
+        S, V = self.n_states, len(self._canon)
+        logw, fin = np.zeros((S, V), dtype=np.float32), np.zeros(S, dtype=np.float32)
+        if self.weighted:
+            for s, row in enumerate(self._tw):
+                for c, w in row.items():
+                    logw[s, c] = w
+            fin[:] = self._fw
+        return logw, fin
 
     def dense_tables(self):
         """(next int32 [S,V], dist int32 [S]), the tables of the grammar-constrained beam search (vocr_ctc_grammar_beam_search):
@@ -439,20 +602,143 @@ class Grammar(object):
         return cls(alphabet, trans, accept, name="regex %r" % pattern)
 
     @classmethod
-    def from_words(cls, alphabet, words):
-        """Accepts exactly the given words (utf-8 strings or index sequences): a trie, minimised."""
+    def from_words(cls, alphabet, words, log_weights=None):
+        """Accepts exactly the given words (utf-8 strings or index sequences): a trie, minimised.  log_weights: one natural-log weight
+        per word (a prior over the closed set; a word given twice keeps its larger weight).  The weights are pushed towards the root
+        as a look-ahead, so that the beam search sees them early: with phi(node) = the largest word weight below the node, the arc
+        root -> child carries phi(child), any other arc phi(child) - phi(parent), and a word's end state final = w - phi(node): the
+        total of a word is its weight."""
         canon = alphabet.canonical_indices()
-        trans, accept = [{}], [False]
-        for w in words:
+        words = list(words)
+        if log_weights is not None:
+            log_weights = [float(w) for w in log_weights]
+            if len(log_weights) != len(words):
+                raise ValueError("from_words: %d log_weights for %d words" % (len(log_weights), len(words)))
+            if not np.isfinite(log_weights).all():
+                raise ValueError("from_words: log_weights must be finite")
+        trans, accept, parent, wword = [{}], [False], [-1], [None]
+        for k, w in enumerate(words):
             s = 0
             for c in _labels(alphabet, canon, w, "from_words"):
                 if c not in trans[s]:
                     trans[s][c] = len(trans)
                     trans.append({})
                     accept.append(False)
+                    parent.append(s)
+                    wword.append(None)
                 s = trans[s][c]
             accept[s] = True
-        return cls(alphabet, trans, accept, name="a trie of %d words" % sum(accept))
+            if log_weights is not None:
+                wword[s] = log_weights[k] if wword[s] is None else max(wword[s], log_weights[k])
+        name = "a trie of %d words" % sum(accept)
+        if log_weights is None:
+            return cls(alphabet, trans, accept, name=name)
+        phi = [float("-inf") if w is None else w for w in wword]
+        for s in range(len(trans) - 1, 0, -1):              # a child has a larger number than its parent
+            phi[parent[s]] = max(phi[parent[s]], phi[s])
+        tw = [{c: (phi[d] if s == 0 else phi[d] - phi[s]) for c, d in row.items()} for s, row in enumerate(trans)]
+        fw = [wword[s] - phi[s] if accept[s] else 0.0 for s in range(len(trans))]
+        return cls(alphabet, trans, accept, name="a weighted " + name[2:], arc_w=tw, final_w=fw)
+
+    @classmethod
+    def boost(cls, alphabet, phrases, bonus):
+        """Contextual biasing (hot words): accepts EVERY labelling, and the weight of a labelling is exactly the sum over the phrases
+        of bonus_p * (the occurrences of p in it, overlapping ones included).  `bonus`: a float or one per phrase (natural-log units:
+        what a hit adds to the beam search's rank, times grammar_weight).  The Aho-Corasick automaton of the phrases as a TOTAL
+        deterministic automaton: every state accepts, so the beam search's distance is 0 everywhere and nothing is pruned.  The weights
+        are shaped so that a partial match is rewarded and a broken one pays it back: with the potential psi(state) = the largest
+        bonus_p * depth / |p| over the phrases p through the state's trie node, an arc carries psi(next) - psi(state) plus the bonuses of
+        the phrases completed on arrival (those reached through suffix links too), and final = -psi(state).  One state per trie node
+        times one arc per class: a table for GrammarBeamDecoder, usually far beyond the sweep kernels' 8192 cells."""
+        canon, every = _classes(alphabet)
+        phrases = [_labels(alphabet, canon, p, "boost") for p in phrases]
+        if not phrases or any(not p for p in phrases):
+            raise ValueError("boost: need at least one phrase and no empty one")
+        bonus = [float(bonus)] * len(phrases) if np.isscalar(bonus) else [float(b) for b in bonus]
+        if len(bonus) != len(phrases):
+            raise ValueError("boost: %d bonuses for %d phrases" % (len(bonus), len(phrases)))
+        if not np.isfinite(bonus).all():
+            raise ValueError("boost: bonuses must be finite")
+        goto, depth, psi, out = [{}], [0], [0.0], [0.0]     # the trie; out: the bonuses of the phrases that END at the node
+        for p, b in zip(phrases, bonus):
+            s = 0
+            for k, c in enumerate(p):
+                if c not in goto[s]:
+                    goto[s][c] = len(goto)
+                    goto.append({})
+                    depth.append(k + 1)
+                    psi.append(float("-inf"))
+                    out.append(0.0)
+                s = goto[s][c]
+                psi[s] = max(psi[s], b * (k + 1) / len(p))
+            out[s] += b
+        n = len(goto)
+        fail, order = [0] * n, []
+        queue = list(goto[0].values())
+        while queue:                                        # breadth first: a node's suffix link is known before its children's
+            following = []
+            for s in queue:
+                order.append(s)
+                for c, d in goto[s].items():
+                    f = fail[s]
+                    while f and c not in goto[f]:
+                        f = fail[f]
+                    fail[d] = goto[f][c] if c in goto[f] and goto[f][c] != d else 0
+                    following.append(d)
+            queue = following
+        done = list(out)                                    # done[s]: the bonuses of every phrase that ends where s is reached
+        for s in order:
+            done[s] = out[s] + done[fail[s]]
+        trans = [None] * n
+        for s in [0] + order:                               # the total transition function, suffix links resolved
+            row = {}
+            for c in every:
+                row[c] = goto[s][c] if c in goto[s] else (trans[fail[s]][c] if s else 0)
+            trans[s] = row
+        tw = [{c: psi[d] - psi[s] + done[d] for c, d in trans[s].items()} for s in range(n)]
+        fw = [-psi[s] for s in range(n)]
+        g = cls(alphabet, trans, [True] * n, name="a boost of %d phrases" % len(phrases), arc_w=tw, final_w=fw,
+                dense_only=n + n * len(every) > ops.GRAMMAR_CELLS_MAX)
+        return g
+
+    @classmethod
+    def from_ngram(cls, lm, scale=1.0, dense_only=False, alphabet=None):
+        """A character n-gram (lm.CharNgramLM) as a weighted automaton: its states are the LM's histories that can be reached from the
+        start, the arc of a state on class c carries scale * ln P(c | history) and leads to the LM's next state, every state accepts
+        with final = scale * ln P(</s> | history).  ln Z under it is ln sum_l P(l | x) * P_LM(l)^scale over ALL labellings (the
+        denominator of MMI / CTC-CRF training), and GrammarBeamDecoder with it and no LM is BeamDecoder with the LM.  The alphabet is
+        the LM's (CharNgramLM.from_arpa keeps it) unless given.  An automaton beyond the sweep kernels' 8192 cells is a ValueError that
+        names the sizes, unless dense_only: then only the beam search's tables are built."""
+        alphabet = alphabet if alphabet is not None else getattr(lm, "alphabet", None)
+        if alphabet is None:
+            raise ValueError("from_ngram: the LM does not know its alphabet; pass alphabet=")
+        canon, every = _classes(alphabet)
+        if lm.logp.shape[1] != len(canon):
+            raise ValueError("from_ngram: the LM was resolved for %d symbols, the alphabet has %d" % (lm.logp.shape[1], len(canon)))
+        scale = float(scale)
+        if not np.isfinite(scale):
+            raise ValueError("from_ngram: scale must be finite")
+        number, order = {int(lm.start): 0}, [int(lm.start)]
+        k = 0
+        while k < len(order):                               # the reachable histories, breadth first, the start as state 0
+            for c in every:
+                d = int(lm.next[order[k], c])
+                if d not in number:
+                    number[d] = len(order)
+                    order.append(d)
+            k += 1
+        S, E = len(order), len(order) * len(every)
+        if S + E > ops.GRAMMAR_CELLS_MAX and not dense_only:
+            raise ValueError("from_ngram: %d LM states x %d classes give %d states + %d arcs, more than the kernel's %d cells "
+                             "(dense_only=True builds the beam search's tables alone)" % (S, len(every), S, E, ops.GRAMMAR_CELLS_MAX))
+        # float32 products, so that scale = 1 hands the beam search the LM's own table entries bit for bit
+        lw = (np.float32(scale) * lm.logp.astype(np.float32)).astype(np.float64)
+        le = (np.float32(scale) * lm.eos.astype(np.float32)).astype(np.float64)
+        trans = [{c: number[int(lm.next[h, c])] for c in every} for h in order]
+        tw = [{c: float(lw[h, c]) for c in every} for h in order]
+        fw = [float(le[h]) for h in order]
+        return cls(alphabet, trans, [True] * S, name="a %d-gram of %d states" % (lm.order, S), arc_w=tw, final_w=fw, as_given=True,
+                   dense_only=dense_only)
 
     @classmethod
     def contains(cls, alphabet, keyword, whole_word=False):
@@ -523,12 +809,32 @@ class Grammar(object):
         return g
 
     @classmethod
-    def from_dfa(cls, alphabet, transitions, accept):
+    def from_dfa(cls, alphabet, transitions, accept, arc_weights=None, final_weights=None):
         """Explicit tables: `transitions[s]` a dict symbol -> state (a symbol is an alphabet index or one utf-8 character), `accept[s]`
-        flags, state 0 the start.  Two symbols of one class must lead to the same state."""
+        flags, state 0 the start.  Two symbols of one class must lead to the same state.  `arc_weights[s]` a dict symbol -> natural-log
+        weight with the keys of transitions[s] and `final_weights[s]` one float per state (read for accepting states) make the grammar
+        weighted; they go together and must be finite, and two symbols of one class must carry the same weight."""
         canon = alphabet.canonical_indices()
         if len(transitions) != len(accept) or not len(accept):
             raise ValueError("from_dfa: need one accept flag per state and at least one state")
+        if (arc_weights is None) != (final_weights is None):
+            raise ValueError("from_dfa: arc_weights and final_weights go together")
+        tw = None
+        if arc_weights is not None:
+            if len(arc_weights) != len(accept) or len(final_weights) != len(accept):
+                raise ValueError("from_dfa: need the arc weights of every state and one final weight per state (%d states, %d rows of "
+                                 "arc weights, %d final weights)" % (len(accept), len(arc_weights), len(final_weights)))
+            tw = []
+            for s, row in enumerate(arc_weights):
+                if set(row) != set(transitions[s]):
+                    raise ValueError("from_dfa: state %d has arcs on %s but weights on %s" % (s, sorted(transitions[s], key=str),
+                                                                                             sorted(row, key=str)))
+                out = {}
+                for sym, w in row.items():
+                    c = _labels(alphabet, canon, sym if isinstance(sym, str) else [sym], "from_dfa")[0]
+                    if out.setdefault(c, float(w)) != float(w) and not (np.isnan(out[c]) and np.isnan(float(w))):
+                        raise ValueError("from_dfa: state %d has two weights on class %d" % (s, c))
+                tw.append(out)
         trans = []
         for s, row in enumerate(transitions):
             out = {}
@@ -540,26 +846,43 @@ class Grammar(object):
                 if out.setdefault(c, d) != d:
                     raise ValueError("from_dfa: state %d is not deterministic on class %d" % (s, c))
             trans.append(out)
-        return cls(alphabet, trans, list(accept), name="dfa of %d states" % len(accept))
+        if tw is None:
+            return cls(alphabet, trans, list(accept), name="dfa of %d states" % len(accept))
+        return cls(alphabet, trans, list(accept), name="weighted dfa of %d states" % len(accept), arc_w=tw,
+                   final_w=[float(f) for f in final_weights])
 
 
 def pack_grammars(grammars, device):
-    """The concatenated tables ops.ctc_grammar_scores takes, on `device`."""
+    """The concatenated tables ops.ctc_grammar_scores takes, on `device`.  "arc_logw" / "final_logw" (fp32, the arcs' and the states'
+    order) are there only when some grammar of the pack is weighted; its unweighted members get zeros."""
+    grammars = list(grammars)
+    for g in grammars:
+        if g.dense_only:
+            raise ValueError("pack_grammars: %s was built with the beam search's dense tables alone (%d states + %d arcs)"
+                             % (g.name, g.n_states, g.n_arcs))
     s_off = np.cumsum([0] + [g.n_states for g in grammars]).astype(np.int32)
     a_off = np.cumsum([0] + [g.n_arcs for g in grammars]).astype(np.int32)
 
     def cat(name):
         return torch.from_numpy(np.concatenate([getattr(g, name) for g in grammars]).astype(np.int32)).to(device)
 
-    return {"state_off": torch.from_numpy(s_off).to(device), "arc_off": torch.from_numpy(a_off).to(device), "src": cat("arc_src"),
-            "cls": cat("arc_cls"), "dst": cat("arc_dst"), "accept": cat("accept"),
-            "max_states": max(g.n_states for g in grammars), "max_arcs": max(g.n_arcs for g in grammars)}
+    out = {"state_off": torch.from_numpy(s_off).to(device), "arc_off": torch.from_numpy(a_off).to(device), "src": cat("arc_src"),
+           "cls": cat("arc_cls"), "dst": cat("arc_dst"), "accept": cat("accept"),
+           "max_states": max(g.n_states for g in grammars), "max_arcs": max(g.n_arcs for g in grammars)}
+    if any(g.weighted for g in grammars):
+        aw = np.concatenate([g.arc_logw if g.weighted else np.zeros(g.n_arcs, dtype=np.float32) for g in grammars] +
+                            [np.zeros(1, dtype=np.float32)])            # one word of padding: never an empty (NULL) table
+        fw = np.concatenate([g.final_logw if g.weighted else np.zeros(g.n_states, dtype=np.float32) for g in grammars])
+        out["arc_logw"] = torch.from_numpy(aw.astype(np.float32)).to(device)
+        out["final_logw"] = torch.from_numpy(fw.astype(np.float32)).to(device)
+    return out
 
 
 def pack_dense_grammars(grammars, device, max_table_bytes=1 << 30):
     """The concatenated dense tables ops.ctc_grammar_beam_search takes, on `device`: state_off int32 [G+1], next int32 [states, V],
-    dist int32 [states].  The sweep kernels' 8192 cells do not bound them; their memory does: tables above max_table_bytes are a
-    ValueError that names the sizes."""
+    dist int32 [states]; and, only when some grammar of the pack is weighted, logw fp32 [states, V] and final fp32 [states]
+    (Grammar.dense_weights; zeros for its unweighted members).  The sweep kernels' 8192 cells do not bound them; their memory does:
+    tables above max_table_bytes are a ValueError that names the sizes."""
     grammars = list(grammars)
     if not grammars:
         raise ValueError("pack_dense_grammars: no grammar")
@@ -568,16 +891,22 @@ def pack_dense_grammars(grammars, device, max_table_bytes=1 << 30):
         raise ValueError("pack_dense_grammars: the grammars are over alphabets of different sizes (%s)"
                          % sorted({len(g._canon) for g in grammars}))
     states = sum(g.n_states for g in grammars)
-    nbytes = states * (V + 1) * 4
+    weighted = any(g.weighted for g in grammars)
+    nbytes = states * (V + 1) * 4 * (2 if weighted else 1)
     if nbytes > max_table_bytes:
         raise ValueError("pack_dense_grammars: %d states x %d symbols of dense tables take %d bytes, more than max_table_bytes=%d"
                          % (states, V, nbytes, max_table_bytes))
     tabs = [g.dense_tables() for g in grammars]
     s_off = np.cumsum([0] + [g.n_states for g in grammars]).astype(np.int32)
-    return {"state_off": torch.from_numpy(s_off).to(device),
-            "next": torch.from_numpy(np.ascontiguousarray(np.concatenate([t[0] for t in tabs], axis=0))).to(device),
-            "dist": torch.from_numpy(np.ascontiguousarray(np.concatenate([t[1] for t in tabs]))).to(device),
-            "num_grammars": len(grammars), "num_states": int(states)}
+    out = {"state_off": torch.from_numpy(s_off).to(device),
+           "next": torch.from_numpy(np.ascontiguousarray(np.concatenate([t[0] for t in tabs], axis=0))).to(device),
+           "dist": torch.from_numpy(np.ascontiguousarray(np.concatenate([t[1] for t in tabs]))).to(device),
+           "num_grammars": len(grammars), "num_states": int(states)}
+    if weighted:
+        wt = [g.dense_weights() for g in grammars]
+        out["logw"] = torch.from_numpy(np.ascontiguousarray(np.concatenate([t[0] for t in wt], axis=0))).to(device)
+        out["final"] = torch.from_numpy(np.ascontiguousarray(np.concatenate([t[1] for t in wt]))).to(device)
+    return out
 
 
 def group_grammars(grammars, T, B, want_best):
@@ -661,7 +990,9 @@ class GrammarMatcher(object):
         return self._canon[key]
 
     def scores(self, model_output, lens, grammars, want_best=True):
-        """Device tensors (logp [B,G], best [B,G], labels [B,G,T], label_lens [B,G]); the last three None without want_best."""
+        """Device tensors (logp [B,G], best [B,G], labels [B,G,T], label_lens [B,G]); the last three None without want_best.  Under a
+        weighted grammar logp is ln Z, a weighted score that is a probability only when the weights normalise, and best is the best
+        path's log-probability plus its weight."""
         grammars = list(grammars)
         dev = model_output.device
         T, B = int(model_output.shape[0]), int(model_output.shape[1])

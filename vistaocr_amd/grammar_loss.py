@@ -9,7 +9,10 @@ csrc/ctc_grammar.hip: score and gradient in one call).  A partial transcript ("k
 position, an unknown single character, or no transcript at all ("this field is a date") become targets.  The chain automaton of one
 labelling gives CTCLoss's value.
 
-WHAT IT IS NOT: there are no weights on the arcs; the automata are built on the host in Python (`to_grammar`, once per distinct target,
+A WEIGHTED grammar from `to_grammar` (Grammar.from_dfa(arc_weights=, final_weights=), from_words(log_weights=): "probably O, possibly
+0") makes P_b the weighted sum Z_b (vocr_ctc_grammar_grad_weighted); the weights themselves get no gradient.
+
+WHAT IT IS NOT: the automata are built on the host in Python (`to_grammar`, once per distinct target,
 kept in a bounded LRU cache) and their tables copied to the device with every batch; an automaton has at most 8192 states + arcs; the
 kernel stores frames x (largest states + largest arcs of the batch) x 4 bytes of forward rows per line (a batch beyond 2 GiB is cut
 into chunks); and no claim about accuracy is made here."""
@@ -26,11 +29,17 @@ from .textutils import utf8_to_uxxxx
 
 
 def pack_batch(grammars, which, act_lens, device):
-    """pack_grammars' tables plus `which` and the lines' frame counts in ONE host-to-device copy: (packed dict, which_dev, lens_dev)."""
+    """pack_grammars' tables plus `which` and the lines' frame counts in ONE host-to-device copy: (packed dict, which_dev, lens_dev).
+    The weight tables of a batch with a weighted grammar travel in the same copy, as the bits of their floats."""
     s_off = np.cumsum([0] + [g.n_states for g in grammars]).astype(np.int32)
     a_off = np.cumsum([0] + [g.n_arcs for g in grammars]).astype(np.int32)
     parts = [s_off, a_off] + [np.concatenate([getattr(g, n) for g in grammars]).astype(np.int32) for n in ("arc_src", "arc_cls", "arc_dst", "accept")]
     parts += [np.asarray(which, dtype=np.int32), np.asarray(act_lens, dtype=np.int32)]
+    weighted = any(g.weighted for g in grammars)
+    if weighted:                                                    # (one word of padding: the arc table is never empty)
+        aw = [g.arc_logw if g.weighted else np.zeros(g.n_arcs, dtype=np.float32) for g in grammars] + [np.zeros(1, dtype=np.float32)]
+        fw = [g.final_logw if g.weighted else np.zeros(g.n_states, dtype=np.float32) for g in grammars]
+        parts += [np.concatenate(aw).astype(np.float32).view(np.int32), np.concatenate(fw).astype(np.float32).view(np.int32)]
     host = torch.from_numpy(np.concatenate(parts))
     if device.type == "cuda":
         host = host.pin_memory()
@@ -41,6 +50,8 @@ def pack_batch(grammars, which, act_lens, device):
         at += p.size
     packed = {"state_off": views[0], "arc_off": views[1], "src": views[2], "cls": views[3], "dst": views[4], "accept": views[5],
               "max_states": max(g.n_states for g in grammars), "max_arcs": max(g.n_arcs for g in grammars)}
+    if weighted:
+        packed["arc_logw"], packed["final_logw"] = views[8].view(torch.float32), views[9].view(torch.float32)
     return packed, views[6], views[7]
 
 

@@ -74,8 +74,9 @@ class CharNgramLM(object):
     """Resolved tables of a character n-gram over the classes of an alphabet (see the module docstring).  numpy arrays:
     `logp` float64 [S, V], `next` int32 [S, V], `eos` float64 [S]; `start` int; `order` N; `states` the history tuples."""
 
-    def __init__(self, logp, nxt, eos, start, order, states):
+    def __init__(self, logp, nxt, eos, start, order, states, alphabet=None):
         self.logp, self.next, self.eos, self.start, self.order, self.states = logp, nxt, eos, int(start), int(order), states
+        self.alphabet = alphabet                          # the alphabet the tables were resolved for (Grammar.from_ngram reads it)
         self._dev = {}
 
     @property
@@ -172,7 +173,7 @@ class CharNgramLM(object):
         if not np.isfinite(logp).all():
             raise ValueError("%s: the resolved LM has non-finite log-probabilities" % path)
         st = sid[("<s>",)] if ("<s>",) in sid else 0
-        return cls(logp[:, :V].copy(), nxt[:, :V].astype(np.int32), logp[:, V].copy(), st, N, states)
+        return cls(logp[:, :V].copy(), nxt[:, :V].astype(np.int32), logp[:, V].copy(), st, N, states, alphabet)
 
     def to(self, device):
         """The device tables (cached per device): {'lm_logp': fp32 [S,V], 'lm_next': int32 [S,V], 'lm_eos': fp32 [S], 'start': int}."""

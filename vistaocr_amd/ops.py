@@ -1294,13 +1294,16 @@ def ctc_beam_search(logits, lens, canon=None, beam=16, nbest=1, lm=None, lm_weig
 
 
 def ctc_grammar_beam_search(logits, lens, dense_packed, which=None, canon=None, beam=16, nbest=1, lm=None, lm_weight=0.0,
-                            insertion_bonus=0.0, prune_logp=None):
+                            insertion_bonus=0.0, prune_logp=None, grammar_weight=1.0, want_grammar=False):
     """Grammar-constrained CTC prefix beam search (vocr_ctc_grammar_beam_search) over raw logits [T,B,V]: ctc_beam_search restricted to
     the labellings that line b's automaton accepts.  `dense_packed`: the device tables of grammar.pack_dense_grammars (state_off int32
     [G+1], next int32 [states,V], dist int32 [states]); `which`: one automaton index per line (any int sequence or tensor; None:
     automaton 0 for every line; an index outside [0, G) gives that line no hypothesis); `lens`, `canon`, `lm` and the weights as for
     ctc_beam_search.  Returns (labels int32 [B,nbest,T], lengths int32 [B,nbest], scores fp32 [B,nbest,3] = total, acoustic, LM), on
-    the device; a rank the search did not fill has length 0 and total -inf."""
+    the device; a rank the search did not fill has length 0 and total -inf.  A pack with the weight tables "logw" fp32 [states,V] and
+    "final" fp32 [states] (pack_dense_grammars adds them when a grammar is weighted) goes to vocr_ctc_grammar_beam_search_weighted: a
+    hypothesis's rank then adds grammar_weight * (the weight of its labelling under the automaton), and total includes it.
+    want_grammar: a fourth result, fp32 [B,nbest], that raw weight (zeros without weight tables)."""
     _need_gpu(logits)
     logits = _f32c(logits)
     T, B, V = logits.shape
@@ -1326,9 +1329,27 @@ def ctc_grammar_beam_search(logits, lens, dense_packed, which=None, canon=None, 
     ws = _ws(nbytes, dev)
     lm_args = _char_lm_args("ctc_grammar_beam_search", lm, V)
     prune = float("-inf") if prune_logp is None else float(prune_logp)
-    call("vocr_ctc_grammar_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(s_off), _p(nxt), _p(dist),
-         G, _p(which_dev), *lm_args, float(lm_weight), float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores), _p(ws),
-         ws.numel() * 4, _stream())
+    logw, fin = dense_packed.get("logw"), dense_packed.get("final")
+    if (logw is None) != (fin is None):
+        raise RuntimeError("ctc_grammar_beam_search: the weight tables logw and final go together")
+    if logw is None:
+        call("vocr_ctc_grammar_beam_search", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(s_off), _p(nxt),
+             _p(dist), G, _p(which_dev), *lm_args, float(lm_weight), float(insertion_bonus), prune, _p(labels), _p(out_lens), _p(scores),
+             _p(ws), ws.numel() * 4, _stream())
+        if want_grammar:
+            return labels, out_lens, scores, torch.zeros(B, int(nbest), dtype=torch.float32, device=dev)
+        return labels, out_lens, scores
+    _need_gpu(logw, fin)
+    if (logw.dtype != torch.float32 or fin.dtype != torch.float32 or tuple(logw.shape) != (states, V) or tuple(fin.shape) != (states,)
+            or not (logw.is_contiguous() and fin.is_contiguous())):
+        raise RuntimeError("ctc_grammar_beam_search: the weight tables do not match the dense tables (logw %s %s, final %s %s, states=%d "
+                           "V=%d)" % (tuple(logw.shape), logw.dtype, tuple(fin.shape), fin.dtype, states, V))
+    out_g = torch.empty(B, int(nbest), dtype=torch.float32, device=dev) if want_grammar else None
+    call("vocr_ctc_grammar_beam_search_weighted", _p(logits), _p(lens_dev), T, B, V, _p(canon), int(beam), int(nbest), _p(s_off), _p(nxt),
+         _p(dist), _p(logw), _p(fin), G, _p(which_dev), *lm_args, float(lm_weight), float(grammar_weight), float(insertion_bonus), prune,
+         _p(labels), _p(out_lens), _p(scores), _p(out_g), _p(ws), ws.numel() * 4, _stream())
+    if want_grammar:
+        return labels, out_lens, scores, out_g
     return labels, out_lens, scores
 
 
@@ -1557,6 +1578,23 @@ GRAMMAR_CELLS_MAX = 8192
 GRAMMAR_BP_MAX_BYTES = 1 << 31
 
 
+def _grammar_weight_tables(who, gp, dev):
+    """(arc_logw, final_logw) of a packed dict, contiguous fp32 device tensors, or (None, None) for an unweighted pack.  The arc table
+    has at least one word (pack_grammars pads it), so that a given table is never a NULL pointer."""
+    aw, fw = gp.get("arc_logw"), gp.get("final_logw")
+    if (aw is None) != (fw is None):
+        raise RuntimeError("%s: grammars_packed has one of arc_logw / final_logw without the other" % who)
+    if aw is None:
+        return None, None
+    _need_gpu(aw, fw)
+    if (aw.dtype != torch.float32 or fw.dtype != torch.float32 or aw.dim() != 1 or fw.dim() != 1 or aw.numel() < max(gp["src"].numel(), 1)
+            or fw.numel() != gp["accept"].numel()):
+        raise RuntimeError("%s: need fp32 arc_logw of at least one word and one per arc and fp32 final_logw of one per state (arc_logw %s "
+                           "%s for %d arcs, final_logw %s %s for %d states)" % (who, tuple(aw.shape), aw.dtype, gp["src"].numel(),
+                                                                               tuple(fw.shape), fw.dtype, gp["accept"].numel()))
+    return aw.contiguous(), fw.contiguous()
+
+
 def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True):
     """CTC grammar search (vocr_ctc_grammar_scores) on raw logits [T,B,V]: for every (line, automaton) the natural log of the exact
     probability that the line's collapsed labelling is accepted - the sum over all frame paths, no beam - and, with `want_best`, the
@@ -1566,7 +1604,7 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
     [states], and the ints "max_states", "max_arcs" (bounds of one automaton's sizes); `canon` int32 [V] device tensor of the symbol
     classes or None.  Returns, on the device, (logp fp32 [B,G]; best fp32 [B,G]; labels int32 [B,G,T]; label_lens int32 [B,G]), the last
     three None without want_best (no max pass runs and no back pointers are allocated; logp has the same bits either way).  -inf / -inf /
-    length -1 where nothing is accepted and, for every line, for an automaton that breaks a rule.  No weights on arcs (the gradient: ctc_grammar_grad); best
+    length -1 where nothing is accepted and, for every line, for an automaton that breaks a rule.  A pack with "arc_logw" [arcs] and "final_logw" [states] (fp32; pack_grammars adds them when a grammar is weighted) goes to vocr_ctc_grammar_scores_weighted: logp is then ln Z, best the best path's log-probability plus its weight (the gradient: ctc_grammar_grad); best
     is the best PATH, not the most probable accepted labelling (ctc_grammar_beam_search / GrammarBeamDecoder search for that).  Shapes, dtypes and the kernel's limits are checked here; the CONTENTS of
     the tables stay on the device and are not read back (that would cost a synchronise per call): the kernel validates every automaton
     against "max_states" / "max_arcs" and its own rules, but state_off[-1] <= accept.numel() and arc_off[-1] <= src.numel() are trusted,
@@ -1600,9 +1638,15 @@ def ctc_grammar_scores(logits, lens, grammars_packed, canon=None, want_best=True
         labels = torch.empty(B, G, T, dtype=torch.int32, device=dev)
         out_lens = torch.empty(B, G, dtype=torch.int32, device=dev)
     ws = _ws(nbytes, dev)
-    call("vocr_ctc_grammar_scores", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G, _p(t["src"]),
-         _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(logp), _p(best), _p(labels), _p(out_lens), T, _p(ws), ws.numel() * 4,
-         _stream())
+    aw, fw = _grammar_weight_tables("ctc_grammar_scores", gp, dev)
+    if aw is None:
+        call("vocr_ctc_grammar_scores", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G, _p(t["src"]),
+             _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(logp), _p(best), _p(labels), _p(out_lens), T, _p(ws), ws.numel() * 4,
+             _stream())
+    else:
+        call("vocr_ctc_grammar_scores_weighted", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G,
+             _p(t["src"]), _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), _p(aw), _p(fw), ms, ma, _p(logp), _p(best), _p(labels),
+             _p(out_lens), T, _p(ws), ws.numel() * 4, _stream())
     return logp, best, labels, out_lens
 
 
@@ -1622,7 +1666,9 @@ def ctc_grammar_grad(logits, lens, grammars_packed, which, canon=None, weights=N
     else fp32 [T,B,V] = the gradient with respect to the raw logits of sum_b weights[b] * logp[b] over the lines with a finite score
     (rows past `lens`, and the rows of a line whose score is -inf, whose automaton breaks a rule or whose which[b] is outside [0, G),
     are zeros).  Without weights only the forward sweep runs and nothing is stored; with them the forward rows are, T * B * (max_states
-    + max_arcs) * 4 bytes, at most 2 GiB per call: GrammarMatcher.line_log_prob cuts a batch that needs more."""
+    + max_arcs) * 4 bytes, at most 2 GiB per call: GrammarMatcher.line_log_prob cuts a batch that needs more.  A weighted pack
+    ("arc_logw", "final_logw": ctc_grammar_scores) goes to vocr_ctc_grammar_grad_weighted: logp is ln Z and dlogits its gradient (none
+    with respect to the weights themselves)."""
     gp = grammars_packed
     names = ("state_off", "arc_off", "src", "cls", "dst", "accept")
     _need_gpu(logits, which, *[gp[k] for k in names])
@@ -1640,7 +1686,9 @@ def ctc_grammar_grad(logits, lens, grammars_packed, which, canon=None, weights=N
     if which.dtype != torch.int32 or tuple(which.shape) != (B,):
         raise RuntimeError("ctc_grammar_grad: which must be int32 [B] (which %s %s, B=%d)" % (tuple(which.shape), which.dtype, B))
     ms, ma = int(gp["max_states"]), int(gp["max_arcs"])
-    nbytes = _lib.load().vocr_ctc_grammar_grad_workspace_bytes(T, B, V, G, ms, ma, 0 if weights is None else 1)
+    aw, fw = _grammar_weight_tables("ctc_grammar_grad", gp, logits.device)
+    ws_bytes = _lib.load().vocr_ctc_grammar_grad_workspace_bytes if aw is None else _lib.load().vocr_ctc_grammar_grad_weighted_workspace_bytes
+    nbytes = ws_bytes(T, B, V, G, ms, ma, 0 if weights is None else 1)
     if nbytes == 0:
         raise RuntimeError("ctc_grammar_grad: unsupported shape (T=%d B=%d V=%d G=%d max_states=%d max_arcs=%d; 2 <= V <= 256, "
                            "max_states >= 1, max_states + max_arcs <= %d, T * B * G < 2^31, with weights T * B * (max_states + "
@@ -1657,9 +1705,14 @@ def ctc_grammar_grad(logits, lens, grammars_packed, which, canon=None, weights=N
     which = which.contiguous()
     logp = torch.empty(B, dtype=torch.float32, device=dev)
     ws = _ws(nbytes, dev)
-    call("vocr_ctc_grammar_grad", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G, _p(t["src"]),
-         _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(which), _p(weights), _p(logp), _p(dlogits), _p(ws), ws.numel() * 4,
-         _stream())
+    if aw is None:
+        call("vocr_ctc_grammar_grad", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G, _p(t["src"]),
+             _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), ms, ma, _p(which), _p(weights), _p(logp), _p(dlogits), _p(ws), ws.numel() * 4,
+             _stream())
+    else:
+        call("vocr_ctc_grammar_grad_weighted", _p(logits), _p(lens_dev), T, B, V, _p(canon), _p(t["state_off"]), _p(t["arc_off"]), G,
+             _p(t["src"]), _p(t["cls"]), _p(t["dst"]), _p(t["accept"]), _p(aw), _p(fw), ms, ma, _p(which), _p(weights), _p(logp),
+             _p(dlogits), _p(ws), ws.numel() * 4, _stream())
     return logp, dlogits
 
 
